@@ -19,6 +19,15 @@ frame is bit-identical to one GPU's).  Total work per step is fixed:
 Each step also resolves the frame to bytes on the device (rt_resolve_u8_device,
 main.scm:481-491), after the gather when N > 1.
 
+A plain run sets up, warms up, times `--steps` frames and prints the result
+line: the headline figure, `ms_per_step` and the timed frames' own counters.
+`--dump-outputs DIR` also writes what the last timed step computed (rank 0's
+frame accumulator and resolved image) as DIR/frame.npy (float64) and
+DIR/image.npy (float32); the scene and the path RNG are seeded, so two builds
+run with the same arguments can be compared output for output.  Everything
+below (parity, the CPU baseline, the roofline objects and the single-lane
+profiling frame) is measured only with `--full`.
+
 Parity (the metric's "per-pixel RMS vs ref"), at every N, after the timed
 steps on rank 0: (1) `parity`: the oracle renders a 64-row band at the top
 sample indices (at N=1 this is also the timed cpu_baseline) and the GPU renders
@@ -124,18 +133,51 @@ def parse():
     p.add_argument("--ny", type=int, default=1080)
     p.add_argument("--scene", default="cover")
     p.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED0002)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the CPU baseline, both parity legs, the single-lane profiling "
+                        "frame and the roofline / PMC report (a plain run prints the headline line only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs (rank 0) as DIR/frame.npy and DIR/image.npy")
     p.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
     p.add_argument("--no-cpu-baseline", action="store_true",
-                   help="skip the CPU baseline and with it the band parity check (both need the oracle)")
+                   help="with --full: skip the CPU baseline and with it the parity checks (both need the oracle)")
     p.add_argument("--no-profile-events", action="store_true")
-    p.add_argument("--no-isolated", action="store_true", help="skip the single-lane profiling frame")
+    p.add_argument("--no-isolated", action="store_true", help="with --full: skip the single-lane profiling frame")
     p.add_argument("--lanes", type=int, default=0, help="render lanes (RT_OPT_LANES); 0 = the library's choice")
     p.add_argument("--exact-libm", default="auto", choices=["auto", "exact", "device"],
                    help="RT_OPT_EXACT_LIBM for the timed frames (bounce directions' sin / cos)")
     p.add_argument("--shard-balance", default="",
                    help="comma-separated shard counts (e.g. 2,4,8): render each tile shard of the frame alone on "
                         "this GPU, print its time and segments (max / mean) and exit; no timed bench line")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6     # --dump-outputs writes at most this much in all
+DUMP_SEED = 0x5EED00D0               # the pixel sample of a frame too large to write whole
+
+
+def dump_outputs(out_dir, frame_np, image_np, nx, ny):
+    """--dump-outputs: what a caller of the timed step receives — the frame accumulator (per-pixel RGB
+    sums over the spp samples, f64) and the resolved image (rt_resolve_u8_device's bytes, written as
+    float32) — as out_dir/frame.npy and out_dir/image.npy, both of shape (pixels, 3), row-major from the
+    frame's first row.  A frame whose two arrays exceed DUMP_BUDGET_BYTES (1920x1080 does: 36 B per
+    pixel) is written at one fixed, seeded subset of its pixels, the same rows of both arrays, in
+    ascending pixel order."""
+    import numpy as np
+    npix = nx * ny
+    frame = frame_np.reshape(npix, 3)
+    image = image_np.reshape(npix, 3)
+    per_pixel = 3 * (8 + 4)
+    keep = (DUMP_BUDGET_BYTES - 65536) // per_pixel         # room for the .npy headers and the directory itself
+    if npix > keep:
+        idx = np.sort(np.random.RandomState(DUMP_SEED).permutation(npix)[:keep])
+        frame, image = frame[idx], image[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame.npy"), np.ascontiguousarray(frame, dtype=np.float64))
+    np.save(os.path.join(out_dir, "image.npy"), np.ascontiguousarray(image, dtype=np.float32))
 
 
 def host_cpu():
@@ -560,13 +602,17 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    last_frame = frame.cpu().numpy() if frame is not None else None
+    oracle_legs = a.full and not a.no_cpu_baseline
+    last_frame = frame.cpu().numpy() if frame is not None and (oracle_legs or a.dump_outputs) else None
+    if a.dump_outputs and frame is not None:
+        dump_outputs(a.dump_outputs, last_frame, image.cpu().numpy(), nx, ny)
+        progress("outputs written to %s" % a.dump_outputs)
     # The timed frames keep two render lanes in flight (one for curve scenes): a kernel's
     # event-bracketed duration there includes the other lane's concurrent kernels.  One more
-    # (untimed) frame with a single lane gives each kernel its own duration; with one lane
-    # already, the timed region's events are the kernels' own.
+    # (untimed) frame with a single lane gives each kernel its own duration (--full); with one
+    # lane already, the timed region's events are the kernels' own.
     iso = None
-    if not a.no_profile_events and not a.no_isolated and lanes > 1:
+    if a.full and not a.no_profile_events and not a.no_isolated and lanes > 1:
         with ctx.options(lanes=1):
             iso = step()[0]
         progress("single-lane profiling frame")
@@ -583,51 +629,59 @@ def main():
     elapsed = float(tmax[0])
     if rank == 0:
         value = segs_all / elapsed / 1e6
-        ext_kernels = extend_kernels(a.scene, gpu.scene_info(h))
-        frame = "%dx%dx%dspp" % (nx, ny, spp)
-        pm, pm_src = load_pmc("extend", a.scene, frame)    # PMC counters of these kernels (tools/profile_round.sh)
-        two_lane = None
-        if iso is not None:
-            roof = extend_roofline(iso.segments, iso.segments - iso.extend_rays, iso.paths,
-                                   iso.extend_launches, iso.ms_extend, pm, ext_kernels,
-                                   "single render lane: one extra untimed frame right after the timed ones "
-                                   "(HIP events on the lane's stream, nothing concurrent)")
-            two_lane = extend_roofline(segs, tail_segs, paths, launches, ms_ext, pm, ext_kernels,
-                                       "timed region, %d render lanes overlapped: launch durations include the "
-                                       "other lane's kernels" % lanes)
-        else:
-            roof = extend_roofline(segs, tail_segs, paths, launches, ms_ext, pm, ext_kernels,
-                                   "timed region, one render lane (HIP events on the lane's stream)")
-        valu = valu_issue = None
-        if pm and roof and pm.get("valu_busy") is not None:
-            # share of SIMD cycles issuing VALU over the extend kernels (rocprofv3 VALUBusy, one bench frame):
-            # the issue-side roofline of these VALU / latency-bound kernels
-            valu_issue = {"bound": "valu_issue", "achieved": round(pm["valu_busy"] / 100.0, 4), "peak": 1.0,
-                          "unit": "fraction of SIMD cycles issuing VALU",
-                          "frac": round(pm["valu_busy"] / 100.0, 4),
-                          "lane_utilization": round(pm["valu_lane_utilization"] / 100.0, 4),
-                          "lds_busy": round(pm["lds_busy"] / 100.0, 4),
-                          "lds_bank_conflict_ratio": round(pm["lds_bank_conflict_ratio"], 4),
-                          "wait_share": round(pm["wait_share"], 4),
-                          "valu_instr_per_segment": round(pm["valu_instr_per_segment"], 2),
-                          "source": "%s (%s, kernels %s)" % (pm_src, pm.get("config", ""), pm["kernel_sha16"])}
-        if pm and roof and pm.get("f64_flops_per_segment"):
-            tf = pm["f64_flops_per_segment"] * roof["rays_per_launch"] / (roof["avg_launch_ms"] * 1e-3) / 1e12
-            valu = {"bound": "valu_f64", "achieved": round(tf, 3), "peak": F64_VALU_PEAK_TFLOPS,
-                    "unit": "TFLOP/s", "frac": round(tf / F64_VALU_PEAK_TFLOPS, 4),
-                    "f64_flops_per_segment": round(pm["f64_flops_per_segment"], 1),
-                    "note": "issued f64 lane-ops from SQ_INSTS_VALU_{ADD,MUL,FMA(x2),TRANS}_F64 x 64"}
-        # the whole path's algorithmic bytes per frame over the frame time: north_star's path-level figure
-        fb = frame_bytes(segs, tail_segs, paths, sh_d0, sh, sh_surv, finish_paths, nx * ny, chunks)
-        fb_step = {k: v / a.steps for k, v in fb.items()}
-        frame_ach = sum(fb.values()) / elapsed / 1e9 if world == 1 else None
-        roof_frame = None
-        if frame_ach is not None:
-            roof_frame = {"bound": "hbm", "achieved": round(frame_ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                          "frac": round(frame_ach / HBM_PEAK_GBS, 5),
-                          "bytes_per_step": {k: round(v) for k, v in fb_step.items()},
-                          "note": "algorithmic bytes of every kernel of the frame (extend + shade + tail + "
-                                  "accumulate + resolve) / ms_per_step"}
+        # the roofline / PMC report (--full): a plain run prints the headline and the timed frames' counters
+        roof = two_lane = roof_frame = roof_shade = valu = valu_issue = pmc_source = None
+        if a.full:
+            ext_kernels = extend_kernels(a.scene, gpu.scene_info(h))
+            frame = "%dx%dx%dspp" % (nx, ny, spp)
+            pm, pm_src = load_pmc("extend", a.scene, frame)    # PMC counters of these kernels (tools/profile_round.sh)
+            if iso is not None:
+                roof = extend_roofline(iso.segments, iso.segments - iso.extend_rays, iso.paths,
+                                       iso.extend_launches, iso.ms_extend, pm, ext_kernels,
+                                       "single render lane: one extra untimed frame right after the timed ones "
+                                       "(HIP events on the lane's stream, nothing concurrent)")
+                two_lane = extend_roofline(segs, tail_segs, paths, launches, ms_ext, pm, ext_kernels,
+                                           "timed region, %d render lanes overlapped: launch durations include the "
+                                           "other lane's kernels" % lanes)
+            else:
+                roof = extend_roofline(segs, tail_segs, paths, launches, ms_ext, pm, ext_kernels,
+                                       "timed region, one render lane (HIP events on the lane's stream)")
+            if pm and roof and pm.get("valu_busy") is not None:
+                # share of SIMD cycles issuing VALU over the extend kernels (rocprofv3 VALUBusy, one bench frame):
+                # the issue-side roofline of these VALU / latency-bound kernels
+                valu_issue = {"bound": "valu_issue", "achieved": round(pm["valu_busy"] / 100.0, 4), "peak": 1.0,
+                              "unit": "fraction of SIMD cycles issuing VALU",
+                              "frac": round(pm["valu_busy"] / 100.0, 4),
+                              "lane_utilization": round(pm["valu_lane_utilization"] / 100.0, 4),
+                              "lds_busy": round(pm["lds_busy"] / 100.0, 4),
+                              "lds_bank_conflict_ratio": round(pm["lds_bank_conflict_ratio"], 4),
+                              "wait_share": round(pm["wait_share"], 4),
+                              "valu_instr_per_segment": round(pm["valu_instr_per_segment"], 2),
+                              "source": "%s (%s, kernels %s)" % (pm_src, pm.get("config", ""), pm["kernel_sha16"])}
+            if pm and roof and pm.get("f64_flops_per_segment"):
+                tf = pm["f64_flops_per_segment"] * roof["rays_per_launch"] / (roof["avg_launch_ms"] * 1e-3) / 1e12
+                valu = {"bound": "valu_f64", "achieved": round(tf, 3), "peak": F64_VALU_PEAK_TFLOPS,
+                        "unit": "TFLOP/s", "frac": round(tf / F64_VALU_PEAK_TFLOPS, 4),
+                        "f64_flops_per_segment": round(pm["f64_flops_per_segment"], 1),
+                        "note": "issued f64 lane-ops from SQ_INSTS_VALU_{ADD,MUL,FMA(x2),TRANS}_F64 x 64"}
+            # the whole path's algorithmic bytes per frame over the frame time: north_star's path-level figure
+            fb = frame_bytes(segs, tail_segs, paths, sh_d0, sh, sh_surv, finish_paths, nx * ny, chunks)
+            fb_step = {k: v / a.steps for k, v in fb.items()}
+            frame_ach = sum(fb.values()) / elapsed / 1e9 if world == 1 else None
+            if frame_ach is not None:
+                roof_frame = {"bound": "hbm", "achieved": round(frame_ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": round(frame_ach / HBM_PEAK_GBS, 5),
+                              "bytes_per_step": {k: round(v) for k, v in fb_step.items()},
+                              "note": "algorithmic bytes of every kernel of the frame (extend + shade + tail + "
+                                      "accumulate + resolve) / ms_per_step"}
+            roof_shade = (shade_roofline(iso.ms_shade, iso.extend_launches, iso.shade_hits_d0, iso.shade_hits,
+                                         iso.shade_survivors, "single render lane frame, as roofline", a.scene, frame)
+                          if iso is not None else
+                          shade_roofline(ms_shade, launches, sh_d0, sh, sh_surv, "timed region, one render lane",
+                                         a.scene, frame))
+            pmc_source = ("%s (kernels %s)" % (pm_src, pm["kernel_sha16"])) if pm else \
+                "none: no PMC summary for these kernels (traffic / valu / valu_issue need " \
+                "tools/profile_round.sh on this kernel source at this frame)"
         render_s = [float(r[0]) / a.steps for r in ranks]
         gather_s = [float(r[1]) / a.steps for r in ranks]
         out = {
@@ -643,15 +697,7 @@ def main():
                                       ("" if world == 1 or backend == "nccl" else " (%s rehearsal)" % backend)},
             "roofline": roof, "roofline_two_lane": two_lane, "roofline_frame": roof_frame,
             "valu": valu, "valu_issue": valu_issue,
-            "roofline_shade": (shade_roofline(iso.ms_shade, iso.extend_launches, iso.shade_hits_d0, iso.shade_hits,
-                                              iso.shade_survivors, "single render lane frame, as roofline", a.scene,
-                                              frame)
-                               if iso is not None else
-                               shade_roofline(ms_shade, launches, sh_d0, sh, sh_surv, "timed region, one render lane",
-                                              a.scene, frame)),
-            "pmc_source": ("%s (kernels %s)" % (pm_src, pm["kernel_sha16"])) if pm else
-                          "none: no PMC summary for these kernels (traffic / valu / valu_issue need "
-                          "tools/profile_round.sh on this kernel source at this frame)",
+            "roofline_shade": roof_shade, "pmc_source": pmc_source,
             "scene_device": scene_device(gpu.scene_info(h)),
             "scene_commit": scene_commit,
             "exact_libm": a.exact_libm,
@@ -673,7 +719,7 @@ def main():
         out["cpu_baseline"] = None
         out["parity"] = None
         out["parity_frame"] = None
-        if not a.no_cpu_baseline:
+        if oracle_legs:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import oracle  # the checker and the CPU baseline only, after the timed region
             host = host_cpu()

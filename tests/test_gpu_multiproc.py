@@ -148,7 +148,7 @@ def test_capi_gather_shards_world1(sched):
 
 def test_bench_two_ranks_self_verifying(tmp_path):
     """bench.py at N=2 under torch.distributed.run (gloo rehearsal: both ranks
-    on cuda:0), launched as a fresh child process: the JSON line reports
+    on cuda:0) with --full, launched as a fresh child process: the JSON line reports
     n_gpus 2, per-rank timings, and both parity legs — a band re-rendered on
     rank 0 and rows of the gathered frame itself — pass against the oracle.
     This is the line the driver's 8-GPU SCALE run prints at every N."""
@@ -160,7 +160,7 @@ def test_bench_two_ranks_self_verifying(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
            "--gpus", "2", "--steps", "1", "--warmup", "0", "--spp", "8", "--nx", "320", "--ny", "180",
-           "--cpu-baseline-seconds", "2"]
+           "--cpu-baseline-seconds", "2", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -2,7 +2,7 @@
 # One GPU pass (run on the GPU box from the repo root), logs under gpurun_out/TAG:
 #   pytest -m gpu (all tests; a test failure does not stop the pass, a crash / time limit does),
 #   smoke(), then each bench command given after the tag (quoted), e.g.
-#   tools/gpu_pass.sh r05b "bench.py" "bench.py --scene curves --spp 256 --steps 1"
+#   tools/gpu_pass.sh r05b "bench.py --full" "bench.py --full --scene curves --spp 256 --steps 1"
 # Every GPU step has its own time limit; after an abort, a segfault or a limit nothing else runs.
 set -o pipefail
 TAG=${1:-pass}
