@@ -347,6 +347,85 @@ int rt_resolve_u8(const double* accum, int nx, int ny, int sample_count, uint8_t
 int rt_resolve_u8_device(int ctx, const double* accum_device, int nx, int ny, int sample_count,
                          uint8_t* out_device, void* stream);
 
+/* ---- adaptive sampling (an extension: the reference declares *max-sample*, main.scm:433, and never
+ * uses it; trace-all always does whole-frame passes) -------------------------------------------------
+ * Opt-in: nothing above changes.  RT_ABI_VERSION stays 7; test RT_HAS_ADAPTIVE for these entry points.
+ *
+ * Each pixel j has three records: accum[3j+c], the running sum S_c as above; accum2[3j+c], the running
+ * sum Q_c of x*x (the product rounded, then the add rounded, in sample order); count[j], the uint32
+ * number of samples taken.  A pixel is *converged* when, in f64, in this operation order, with
+ * n = (double)count[j]:
+ *
+ *     d_c = Q_c - (S_c*S_c)/n            c = 0,1,2
+ *     v_c = (d_c < 0 ? 0 : d_c) / (n*(n-1))      a rounding-negative variance clamps to 0, a NaN stays
+ *     e2  = (v_0 + v_1) + v_2            the squared standard error of the pixel mean, channels summed
+ *     m   = ((S_0 + S_1) + S_2) / n
+ *     b   = m > floor ? m : floor
+ *     r   = tol*b
+ *     converged  <=>  e2 <= r*r
+ *
+ * A NaN in e2 or r compares false (so does n < 2: 0/0), and such a pixel keeps sampling until max_spp.
+ * The library is built without FMA contraction, so the rule is reproducible bit for bit on the host
+ * (rtamd.adaptive.converged is the NumPy restatement).
+ *
+ * rt_render_pixels_device: passes spp_begin .. spp_begin+spp_count-1 of the n pixels listed in
+ *   pix_device (device memory) only.  List entries are unique and < nx*ny: the range is checked (a
+ *   read-only pass over the list, before any kernel that writes through it is launched; an entry
+ *   >= nx*ny fails the call with the buffers untouched), the uniqueness is the caller's responsibility.
+ *   Pixels not in the list are neither read nor written, in any of the three buffers.  A listed pixel's
+ *   new samples are exactly those rt_render_device would add for the same passes; accum2 (nullable) gets
+ *   their squares, count (nullable) rises by spp_count.  Lanes, chunking, the tail threshold and every
+ *   kernel choice apply to a list of any length >= 1 as they do to a frame; with n == 0 or
+ *   spp_count == 0 the call does nothing.  The list must stay unchanged during the call.
+ * rt_adaptive_select_device: pix_out = the entries of pix_in[0..n) that are NOT converged under (tol,
+ *   floor), in pix_in's order (a stable compaction: a list in 16x16-tile order stays in it); pix_in NULL
+ *   means pixels 0..n-1.  *out_n = their number; *out_capped = how many of them have count >= max_spp
+ *   (pixels a driver stops sampling unconverged).  pix_out holds n entries, must not overlap pix_in, and
+ *   is written in [0, *out_n) only.  The entries index accum / accum2 / count, whose extent the call does
+ *   not know: their range is the caller's responsibility.  Synchronises the stream.
+ * rt_render_adaptive_device / rt_render_adaptive (host buffers, PCIe-inclusive): overwrite all three
+ *   buffers (nx*ny*3, nx*ny*3, nx*ny).  Round 0 renders passes [0, min_spp) of every pixel, in the
+ *   full-frame tile order; each later round the next batch_spp passes (the last cut at max_spp) of the
+ *   still-active pixels only; after every round, the final one included, the selection compacts the
+ *   active list on the device and two counters are read back (one small copy, one synchronise per
+ *   round).  It stops when the list is empty or max_spp is reached.  Afterwards a pixel's accum equals
+ *   rt_render_device of passes 0..count[j]-1 at that pixel, bit for bit, and count[j] is min_spp plus a
+ *   multiple of batch_spp, or max_spp.  rt_get_stats then reports the rounds together (no kernel times).
+ *   `out` receives the result record and may be NULL.
+ *   Not available over tile shards or several GPUs (the active set would unbalance the deal).
+ * After a failed call the buffers are unspecified.  Refused before any device work: null pointers,
+ * min_spp < 2, max_spp < min_spp, batch_spp < 1, tol or floor negative or not finite, n < 0 or
+ * n > nx*ny, bad handles.
+ * rt_resolve_u8_counts(_device): the resolve above with each pixel's own count,
+ *   floor(255.99*min(1, sqrt(accum[i]/count[i/3]))); a pixel with count 0 resolves to 0. */
+#define RT_HAS_ADAPTIVE 1
+typedef struct rt_adaptive {
+    uint32_t min_spp, max_spp, batch_spp, reserved;
+    double tol, floor;
+} rt_adaptive;
+typedef struct rt_adaptive_result {
+    uint32_t rounds, reserved;
+    uint64_t samples;            /* sum of count[] */
+    uint64_t pixels_converged;   /* pixels that left the active list */
+    uint64_t pixels_capped;      /* pixels still not converged at max_spp */
+    double   ms_total;           /* wall time of the call's device part */
+    double   ms_select;          /* of it: the selections with their readbacks */
+} rt_adaptive_result;
+int rt_render_pixels_device(int scene, int nx, int ny, const uint32_t* pix_device, int64_t n,
+                            int spp_begin, int spp_count, uint64_t seed,
+                            double* accum, double* accum2 /*nullable*/, uint32_t* count /*nullable*/, void* stream);
+int rt_adaptive_select_device(int ctx, const uint32_t* pix_in /*nullable*/, int64_t n,
+                              const double* accum, const double* accum2, const uint32_t* count,
+                              double tol, double floor, uint32_t max_spp,
+                              uint32_t* pix_out, int64_t* out_n, int64_t* out_capped, void* stream);
+int rt_render_adaptive_device(int scene, int nx, int ny, const rt_adaptive* p, uint64_t seed,
+                              double* accum, double* accum2, uint32_t* count, void* stream, rt_adaptive_result* out);
+int rt_render_adaptive(int scene, int nx, int ny, const rt_adaptive* p, uint64_t seed,
+                       double* accum_host, double* accum2_host, uint32_t* count_host, rt_adaptive_result* out);
+int rt_resolve_u8_counts(const double* accum, const uint32_t* count, int nx, int ny, uint8_t* out);
+int rt_resolve_u8_counts_device(int ctx, const double* accum_device, const uint32_t* count_device,
+                                int nx, int ny, uint8_t* out_device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,18 @@ class RtSceneInfo(ctypes.Structure):
                 ("commit_threads", ctypes.c_int32), ("reserved0", ctypes.c_int32)]
 
 
+class RtAdaptive(ctypes.Structure):
+    """rt_adaptive: the adaptive render's rounds (min / max / batch passes) and stop rule (tol, floor)."""
+    _fields_ = [("min_spp", ctypes.c_uint32), ("max_spp", ctypes.c_uint32), ("batch_spp", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("tol", ctypes.c_double), ("floor", ctypes.c_double)]
+
+
+class RtAdaptiveResult(ctypes.Structure):
+    _fields_ = [("rounds", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("samples", ctypes.c_uint64),
+                ("pixels_converged", ctypes.c_uint64), ("pixels_capped", ctypes.c_uint64),
+                ("ms_total", ctypes.c_double), ("ms_select", ctypes.c_double)]
+
+
 # name -> argtypes (restype is always c_int status, except where noted)
 _SIGNATURES = {
     "rt_abi_version": [],
@@ -135,6 +147,23 @@ _SIGNATURES = {
                          ctypes.POINTER(ctypes.c_int64)],
     "rt_gather_shards_local": [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p],
+    # adaptive sampling (RT_HAS_ADAPTIVE)
+    "rt_render_pixels_device": [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.c_void_p, ctypes.c_void_p],
+    "rt_adaptive_select_device": [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_uint32,
+                                  ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                  ctypes.c_void_p],
+    "rt_render_adaptive_device": [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RtAdaptive),
+                                  ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.POINTER(RtAdaptiveResult)],
+    "rt_render_adaptive": [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RtAdaptive), ctypes.c_uint64,
+                           _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_uint32),
+                           ctypes.POINTER(RtAdaptiveResult)],
+    "rt_resolve_u8_counts": [_c_double_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.c_int, _c_u8_p],
+    "rt_resolve_u8_counts_device": [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_void_p, ctypes.c_void_p],
 }
 
 #: every symbol include/rt.h declares (tests check the .so exports all of them)

@@ -294,6 +294,84 @@ def resolve_u8_device(accum_ptr, nx, ny, sample_count, out_ptr, stream=None, ctx
          ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0))
 
 
+def _u64(seed):
+    return ctypes.c_uint64(seed & (2**64 - 1))
+
+
+def _result_dict(r):
+    return {name: getattr(r, name) for name, _ in r._fields_ if name != "reserved"}
+
+
+def adaptive_params(tol, min_spp=16, max_spp=1024, batch_spp=16, floor=0.05):
+    """An rt_adaptive record (include/rt.h, "adaptive sampling")."""
+    return _lib.RtAdaptive(int(min_spp), int(max_spp), int(batch_spp), 0, float(tol), float(floor))
+
+
+def render_pixels_device(scene, nx, ny, pix_ptr, n, spp_begin, spp_count, seed, accum_ptr, accum2_ptr=None,
+                         count_ptr=None, stream=None, ctx=None):
+    """rt_render_pixels_device: passes of the n pixels listed at device pointer pix_ptr (uint32, unique,
+    < nx*ny) into full-frame device buffers: accum, and optionally the squares' sums and sample counts."""
+    h = upload(scene, ctx)
+    call("rt_render_pixels_device", h, nx, ny, ctypes.c_void_p(pix_ptr), int(n), spp_begin, spp_count, _u64(seed),
+         ctypes.c_void_p(accum_ptr), ctypes.c_void_p(accum2_ptr or 0), ctypes.c_void_p(count_ptr or 0),
+         ctypes.c_void_p(stream or 0))
+    return h
+
+
+def adaptive_select_device(pix_in_ptr, n, accum_ptr, accum2_ptr, count_ptr, tol, floor, max_spp, pix_out_ptr,
+                           stream=None, ctx=None):
+    """rt_adaptive_select_device: the not-converged entries of the list at pix_in_ptr (None: pixels 0..n-1)
+    to pix_out_ptr, in order; returns (their number, how many of them have count >= max_spp)."""
+    ctx = ctx or default_context()
+    m, capped = ctypes.c_int64(0), ctypes.c_int64(0)
+    call("rt_adaptive_select_device", ctx.handle, ctypes.c_void_p(pix_in_ptr or 0), int(n), ctypes.c_void_p(accum_ptr),
+         ctypes.c_void_p(accum2_ptr), ctypes.c_void_p(count_ptr), float(tol), float(floor), int(max_spp),
+         ctypes.c_void_p(pix_out_ptr), ctypes.byref(m), ctypes.byref(capped), ctypes.c_void_p(stream or 0))
+    return m.value, capped.value
+
+
+def render_adaptive_device(scene, nx, ny, params, seed, accum_ptr, accum2_ptr, count_ptr, stream=None, ctx=None):
+    """rt_render_adaptive_device: the adaptive render into device buffers (all three overwritten);
+    params = adaptive_params(...).  Returns the result record as a dict."""
+    h = upload(scene, ctx)
+    res = _lib.RtAdaptiveResult()
+    call("rt_render_adaptive_device", h, nx, ny, ctypes.byref(params), _u64(seed), ctypes.c_void_p(accum_ptr),
+         ctypes.c_void_p(accum2_ptr), ctypes.c_void_p(count_ptr), ctypes.c_void_p(stream or 0), ctypes.byref(res))
+    return _result_dict(res)
+
+
+def render_adaptive_host(scene, nx, ny, params, seed, ctx=None):
+    """rt_render_adaptive: returns (accum, accum2, count, result dict) as new host arrays."""
+    h = upload(scene, ctx)
+    accum = np.zeros(nx * ny * 3)
+    accum2 = np.zeros(nx * ny * 3)
+    count = np.zeros(nx * ny, dtype=np.uint32)
+    res = _lib.RtAdaptiveResult()
+    call("rt_render_adaptive", h, nx, ny, ctypes.byref(params), _u64(seed),
+         accum.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), accum2.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+         count.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(res))
+    return accum, accum2, count, _result_dict(res)
+
+
+def resolve_u8_counts(accum, count, nx, ny):
+    """rt_resolve_u8_counts on the host: sqrt(sum / the pixel's own count), 0 where the count is 0."""
+    a = np.ascontiguousarray(accum, dtype=np.float64).ravel()
+    c = np.ascontiguousarray(count, dtype=np.uint32).ravel()
+    if a.size != nx * ny * 3 or c.size != nx * ny:
+        raise ValueError("accum must have nx*ny*3 elements and count nx*ny")
+    out = np.zeros(nx * ny * 3, dtype=np.uint8)
+    call("rt_resolve_u8_counts", a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+         c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), nx, ny, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    return out
+
+
+def resolve_u8_counts_device(accum_ptr, count_ptr, nx, ny, out_ptr, stream=None, ctx=None):
+    """rt_resolve_u8_counts_device on device buffers: nx*ny*3 doubles and nx*ny counts -> bytes."""
+    ctx = ctx or default_context()
+    call("rt_resolve_u8_counts_device", ctx.handle, ctypes.c_void_p(accum_ptr), ctypes.c_void_p(count_ptr), nx, ny,
+         ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0))
+
+
 def curve_depth_probe(cps, eps8, ctx=None):
     """rt_curve_depth_probe: the curve kernels' depth estimate (bez_maxd) for ray-space control points
     cps (n, 12) and 8 eps (n,); returns int32 depths."""

@@ -8,7 +8,8 @@ with sqrt(sum/sample_count).  ``trace_line(scene, y, sample_count)`` is the
 reference's per-row pass (main.scm:452-469) and ``animate(scene)`` its GLUT
 display step (main.scm:533-544: one row per call, then the next pass).
 ``render(scene, spp)`` runs many passes in one GPU call (same result as spp
-successive trace_all calls).
+successive trace_all calls).  ``render_adaptive(scene, tol, ...)`` is an
+extension: passes per pixel until its estimated error is below ``tol``.
 """
 import numpy as np
 
@@ -24,6 +25,9 @@ class Renderer:
         self.ctx = ctx
         self.raw_data = np.zeros(self.size_x * self.size_y * 3, dtype=np.float64)
         self.image = np.zeros(self.size_x * self.size_y * 3, dtype=np.uint8)
+        # render_adaptive only: the running sums of the samples' squares and each pixel's sample count
+        self.raw_data2 = np.zeros(self.size_x * self.size_y * 3, dtype=np.float64)
+        self.counts = np.zeros(self.size_x * self.size_y, dtype=np.uint32)
         self.sample_count = 0
         self.current_y = 0            # *current-y* (main.scm:431)
         self.anim_sample_count = 1    # *sample-count* (main.scm:531)
@@ -68,6 +72,20 @@ class Renderer:
         self.sample_count = spp_begin + spp
         self.image = gpu.resolve_u8(self.raw_data, self.size_x, self.size_y, self.sample_count)
         return self.image
+
+    def render_adaptive(self, scene, tol, min_spp=16, max_spp=1024, batch_spp=16, floor=0.05):
+        """An adaptive render from pass 0 (no counterpart in the reference, whose *max-sample*,
+        main.scm:433, is never used): every pixel gets min_spp passes, then batch_spp more per round while
+        the standard error of its mean exceeds tol * max(mean, floor), up to max_spp.  Fills raw_data,
+        raw_data2 (the squares' sums), counts and image (each pixel resolved with its own count);
+        sample_count becomes max(counts).  Returns the result record (rounds, samples, pixels_converged,
+        pixels_capped, ms_total, ms_select)."""
+        p = gpu.adaptive_params(tol, min_spp, max_spp, batch_spp, floor)
+        self.raw_data, self.raw_data2, self.counts, res = gpu.render_adaptive_host(
+            scene, self.size_x, self.size_y, p, self.seed, self.ctx)
+        self.image = gpu.resolve_u8_counts(self.raw_data, self.counts, self.size_x, self.size_y)
+        self.sample_count = int(self.counts.max())
+        return res
 
     def save_as_ppm(self, path="test.ppm"):
         """main.scm:439-450 — P3, rows written top-down (flipping y-up rows)."""
