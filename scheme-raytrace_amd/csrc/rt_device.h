@@ -156,7 +156,7 @@ struct DevScene {
     // BVH4 of the same tree (curve trees only, else nullptr): its walk pushes up to three children per
     // node, stack4 entries at most; entries past the LDS stack (lds4) go to stk_ovf, stack4 - lds4
     // words per lane of a grid of at most ovf_lanes lanes (entry e of lane g at e * lanes + g);
-    // the buffer holds one such region per render lane and each launch gets its lane's (rt_api.cpp)
+    // the buffer holds one such region per render lane and each launch gets its lane's (rt_render.cpp)
     const BvhNode4* bvh4;  int32_t n_bvh4;
     // k_extend_curves' survivor rings: per resident wave kBezRing entries of 128 B (a root-culled curve's
     // ray-space control points and widths, written by stage A, read by stage B's refills and takes)

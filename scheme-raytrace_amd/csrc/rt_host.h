@@ -1,0 +1,265 @@
+// rt_host.h — what librtamd's host translation units share: the object model behind the handles of
+// include/rt.h, the handle registry, error reporting, the entry points' common prologues and the
+// functions the units call in each other.
+//   rt_scene.cpp     contexts, options, the scene builder, statistics
+//   rt_commit.cpp    flattening, BVH build, upload (commit_scene)
+//   rt_render.cpp    the render scheduler (render_impl) and the render / probe / resolve entry points
+//   rt_gather.cpp    the frame-end gather (RCCL and in-process)
+//   rt_adaptive.cpp  adaptive sampling
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/rt.h"
+#include "rt_device.h"
+
+namespace rtamd {
+
+// rt_last_error's text for the calling thread (rt_scene.cpp); returns 1, the entry points' error code
+int fail(const std::string& msg);
+
+#define HIPCHK(expr)                                                                   \
+    do {                                                                               \
+        hipError_t e_ = (expr);                                                        \
+        if (e_ != hipSuccess)                                                          \
+            return fail(std::string(#expr) + ": " + hipGetErrorString(e_));            \
+    } while (0)
+
+// ------------------------------------------------------------- objects
+enum ObjType { O_SPHERE, O_MSPHERE, O_RECT, O_FLIP, O_BOX, O_TRANSLATE, O_ROTATE_Y, O_LIST, O_BVH, O_BEZIER, O_MEDIUM, O_KLEIN };
+
+struct Obj {
+    ObjType type;
+    int mat = -1, child = -1, axis = 0;
+    std::vector<int> kids;
+    double c0[3] = {0, 0, 0}, c1[3] = {0, 0, 0};
+    double r = 0, t0 = 0, t1 = 0;
+    double a0 = 0, a1 = 0, b0 = 0, b1 = 0, k = 0;
+    double sin_t = 0, cos_t = 1;
+    double cp[12] = {0};       // O_BEZIER control points a, b, c, d
+    double width = 0;
+};
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t ensure(size_t n) {
+        if (n <= bytes) return hipSuccess;
+        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
+        hipError_t e = hipMalloc(&p, n);
+        if (e == hipSuccess) bytes = n;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+
+// A lane = one path pool + stream.  render_impl deals the sample chunks of a
+// render to the lanes round-robin and keeps them in flight together, so the
+// long, narrow tail of one chunk (its last few paths bouncing to depth 100)
+// overlaps the wide first iterations of the next one instead of leaving the
+// chip mostly idle.  Accumulation stays in chunk (= sample) order.
+constexpr int kLanes = 4;                  // most lanes a render may use (RT_OPT_LANES)
+constexpr int kCurveLdsStack = RT_CURVE_LDS_STACK;   // k_extend_curves' BVH4 stack entries in LDS per lane
+struct Lane {
+    DevBuf st_a, st_b, hit, sb, counts, seg_tail;
+    uint32_t* h_counts = nullptr;              // pinned survivor counts, one row per iteration
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_cnt = nullptr;               // the last iteration's survivor counts are on the host
+    hipEvent_t ev_acc = nullptr;               // this lane's last accumulate
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};             // profiling: extend / shade brackets
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_fin;      // profiling: tail kernel brackets
+    size_t n_fin = 0;
+    // the chunk in flight
+    enum State { IDLE, RUNNING, DONE } state = IDLE;
+    int chunk = -1, depth = 0;
+    int index = 0;                             // the lane's position in Context::lanes
+    bool fused_camera = false;                 // depth 0 runs k_camera (no raygen pass)
+    uint32_t n = 0, S = 0;
+    uint64_t seq = 0;                          // enqueue order of the pending iteration
+    RenderParams rp{};
+    PathState A{}, B{}, *cur = nullptr, *nxt = nullptr;
+    QView view{nullptr, 0};
+    ~Lane() {
+        if (h_counts) (void)hipHostFree(h_counts);
+        for (hipEvent_t e : {ev_cnt, ev_acc, ev[0], ev[1], ev[2]}) if (e) (void)hipEventDestroy(e);
+        for (auto& pr : ev_fin) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+// The frame-end gather's layout for one frame size and world (rt_gather_layout): per rank its shard's
+// pixel count and the offset of its pixels in the ranks' concatenated pixel lists (rt_shard_pixels order,
+// ranks in order).  The root (rank 0) also keeps that concatenated list on the device and a receive
+// buffer for the other ranks' compact accumulators: rank r's lands at doubles recv_at(r).  Both gathers —
+// over RCCL (rt_gather_shards) and within one process (rt_gather_shards_local) — fill it the same way and
+// place it with the same kernel (gather_place).
+struct GatherPlan {
+    int nx = -1, ny = -1, world = 0;
+    bool root = false;
+    std::vector<int64_t> count, off;
+    DevBuf pix, recv;
+    size_t recv_at(int r) const { return 3 * (size_t)(off[r] - count[0]); }
+    int64_t others() const { return off[world - 1] + count[world - 1] - count[0]; }
+};
+
+// A context owns the render lanes' path pools: every scene rendered on it
+// shares them (the C ABI renders one scene at a time per context), so a
+// second scene does not take a second 65 % of device memory.
+// The render schedule's knobs are options of the context (rt_context_set_option,
+// include/rt.h RT_OPT_*), 0 = the library's automatic choice.
+struct Context {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    DevBuf accum_tmp, img_tmp;
+    size_t pool_cap = 0;                       // paths per chunk (max_paths), fixed at the first render
+    int pool_lanes = 0;                        // the lanes pool_cap was sized for
+    std::unique_ptr<Lane> lanes[kLanes];       // rt_context_release_pools frees them
+    int64_t opt_lanes = 0;                     // RT_OPT_LANES (0: 2, or 1 for curve-kernel scenes)
+    int64_t opt_max_paths = 0;                 // RT_OPT_MAX_PATHS (0: sized from free memory)
+    int64_t opt_tail_paths = 0;                // RT_OPT_TAIL_PATHS (0: 32768)
+    int64_t opt_tail_div = 0;                  // RT_OPT_TAIL_DIV (0: 256)
+    bool wavefront_only = false;               // RT_OPT_TAIL_OFF: no tail kernel (tests, A/B)
+    GatherPlan gplan;                          // rt_gather_shards_local's plan (the frame size last gathered)
+    int64_t opt_exact_libm = RT_LIBM_AUTO;     // RT_OPT_EXACT_LIBM: the bounce directions' sin / cos
+    // adaptive sampling: the two active-pixel lists a render alternates between, the selection's block
+    // counts / offsets and its two result words (with the range check's word after them), and the host
+    // entry point's device copies of accum2 / count
+    DevBuf sel_list[2], sel_scratch, sel_words, accum2_tmp, count_tmp;
+};
+
+struct Scene {
+    int ctx = -1;
+    std::vector<DevTexture> texs;
+    std::vector<DevMaterial> mats;
+    std::vector<Obj> objs;
+    double cam[RT_CAMERA_DOUBLES] = {0};
+    bool have_cam = false;
+    int sky = RT_SKY_GRADIENT;
+    int light = -1;                   // rt_set_light_sampling target (-1: off)
+    std::vector<double> ranvec;
+    std::vector<int32_t> perm;
+    bool have_perlin = false;
+    bool committed = false;
+
+    // flattened + uploaded
+    DevScene dev{};
+    DevBuf d_sph, d_msph, d_rect, d_bez, d_klein, d_med, d_bgroups, d_groups, d_chains, d_leaves, d_mats, d_texs, d_ranvec, d_perm, d_bvh2, d_bleaf;
+    DevBuf d_fbvh2, d_fbleaf, d_fsph, d_fid;      // time-0 BVH (commit_scene)
+    DevBuf d_bvh4, d_stk_ovf, d_bez_ring, d_fuse_ring;         // curve trees: BVH4, the walk's stack overflow, rings
+    DevBuf d_dev;                                  // a device copy of `dev` (kernels that take the scene by pointer)
+    DevBuf d_leaf_cls;
+    size_t ext_lds = 0;                            // k_extend_lds: LDS bytes (0 = not used) and grid cap
+    uint32_t ext_lds_blocks = 0;
+    size_t cam_lds = 0;                            // k_camera (fused raygen + depth-0 extend), same
+    uint32_t cam_blocks = 0;
+    // render buffers (the lanes' path pools belong to the context)
+    DevBuf pixlist;
+    int pix_nx = -1, pix_ny = -1, pix_y0 = -1, pix_y1 = -1, pix_shard = -1, pix_nshard = -1;
+    uint32_t pix_n = 0;
+    bool profiling = false;
+    rt_stats stats{};
+    double commit_ms = 0.0, commit_upload_ms = 0.0;   // rt_scene_commit: wall time, of it device allocation + copies
+    double commit_sah_ms = 0.0;                        // ... and the SAH builds (commit_threads host threads)
+    int commit_threads = 1;
+};
+
+// ------------------------------------------------------------ registry
+// (rt_scene.cpp; communicators live in rt_gather.cpp, the only unit that knows RCCL)
+extern std::mutex g_mu;
+extern std::map<int, std::unique_ptr<Context>> g_ctx;
+extern std::map<int, std::unique_ptr<Scene>> g_scene;
+
+inline Context* get_ctx(int h) {
+    auto it = g_ctx.find(h);
+    return it == g_ctx.end() ? nullptr : it->second.get();
+}
+inline Scene* get_scene(int h) {
+    auto it = g_scene.find(h);
+    return it == g_scene.end() ? nullptr : it->second.get();
+}
+
+// ----------------------------------------------------------- prologues
+// An entry point's first steps.  The LOCK_* ones hold the registry lock for the rest of the call.
+#define LOCK_SCENE(s, h)                                                        \
+    std::lock_guard<std::mutex> lk_(g_mu);                                      \
+    Scene* s = get_scene(h);                                                    \
+    if (!s) return fail("invalid scene handle");
+#define LOCK_CTX(c, h)                                                          \
+    std::lock_guard<std::mutex> lk_(g_mu);                                      \
+    Context* c = get_ctx(h);                                                    \
+    if (!c) return fail("invalid context handle");
+// the scene builder's: a committed scene takes no more changes
+#define SCENE_OR_FAIL(s, h)                                                     \
+    std::lock_guard<std::mutex> lk_(g_mu);                                      \
+    Scene* s = get_scene(h);                                                    \
+    if (!s) return fail("invalid scene handle " + std::to_string(h));            \
+    if (s->committed) return fail("scene " + std::to_string(h) + " already committed");
+// scene s's context
+#define CTX_OF(c, s)                                                            \
+    Context* c = get_ctx(s->ctx);                                               \
+    if (!c) return fail("scene's context was destroyed");
+// context c's device made current, and st = the caller's stream or, for null, the context's
+#define CTX_STREAM(c, st, stream)                                               \
+    HIPCHK(hipSetDevice(c->device));                                            \
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+
+inline int check_tex(Scene* s, int t) {
+    if (t < 0 || t >= (int)s->texs.size()) return fail("invalid texture id " + std::to_string(t));
+    return 0;
+}
+inline int check_mat(Scene* s, int m) {
+    if (m < 0 || m >= (int)s->mats.size()) return fail("invalid material id " + std::to_string(m));
+    return 0;
+}
+inline int check_obj(Scene* s, int o) {
+    if (o < 0 || o >= (int)s->objs.size()) return fail("invalid object id " + std::to_string(o));
+    return 0;
+}
+inline int check_frame(int nx, int ny) {
+    if (nx <= 0 || ny <= 0) return fail("image size must be positive");
+    if ((uint64_t)nx * (uint64_t)ny >= (1ull << 31)) return fail("image too large");
+    return 0;
+}
+
+// ------------------------------------------------------------- between units
+// rt_commit.cpp: flatten the object tree under `world`, build its BVHs, upload the device scene
+int commit_scene(Scene* s, int world);
+
+// The pixels a render covers: rows [y0, y1) of the frame (trace-all: every
+// row; trace-line, main.scm:452-469: one row), restricted to shard `shard` of
+// `nshard` interleaved 16x16 tiles (the diagonal deal of make_pixlist: tile
+// (x, y) -> shard (x + k y) % nshard).  Listed tile by tile in row-major
+// tile order, pixel j = y*nx + x.
+struct PixSel { int y0, y1, shard, nshard; };
+PixSel full_frame(int ny);
+std::vector<uint32_t> make_pixlist(int nx, int ny, const PixSel& ps);
+
+// A render's pixels on the device: n unique entries pix[q] = image pixel j < nx*ny, in the order the
+// samples are laid out.  The accumulator is indexed by j, or by q when `compact`.  A render also adds
+// its samples' squares to accum2 and their number to count where given (each nullable, never compact).
+struct PixSet {
+    const uint32_t* pix;
+    uint32_t n;
+    bool compact;
+    double* accum2;
+    uint32_t* count;
+};
+// rt_render.cpp: passes spp_begin .. spp_begin+spp_count-1 of the pixels of px into accum
+int render_impl(Scene* s, int nx, int ny, const PixSet& px, int spp_begin, int spp_count, uint64_t seed,
+                double* accum, hipStream_t stream);
+
+}  // namespace rtamd

@@ -1,0 +1,87 @@
+// rt_launch.h — the launch interface of librtamd's device translation units: every function the host
+// translation units call into rt_kernels.hip (path tracing) and rt_frame.hip (frame buffers), declared
+// once.  The device files that define these include it, so a definition that drifts from its
+// declaration is a compile or link error (the library links with -z defs), not a load-time one.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "rt_device.h"
+
+namespace rtamd {
+
+// ------------------------------------------------------- rt_kernels.hip
+hipError_t launch_raygen(const DevScene& sc, const RenderParams& rp, const PathState& st, hipStream_t s);
+// in: the survivor queue view of the previous depth (contiguous for raygen's output); counts: this
+// iteration's [material][shard] hit counters; claim: the persistent curve kernel's next-ray counter
+// (null: per-ray k_extend only); fuse: non-null runs every depth >= 1 in this launch (curve-kernel scenes)
+hipError_t launch_extend(const DevScene& sc, const DevScene* scd, const RenderParams& rp, const PathState& st,
+                         const QView& in, uint32_t n, const HitBuf& hit, uint32_t shard_cap, uint32_t* counts,
+                         bool depth0, unsigned int* claim, const CurveFuse* fuse, hipStream_t s);
+// mat: the material whose hit queue (qv, at most n_upper hits) is shaded; out / out_counts: the next
+// depth's path state and its per-shard survivor counters
+hipError_t launch_shade(int mat, const DevScene& sc, const DevScene* scd, const RenderParams& rp, const PathState& in,
+                        const HitBuf& hit, const QView& qv, uint32_t n_upper, const PathState& out,
+                        uint32_t* out_counts, uint32_t shard_cap, uint32_t depth, hipStream_t s);
+// the tail kernel: finishes the n live paths of `in`; seg_count: its segment counter, followed by the
+// next-path claim; tree0_budget: LDS bytes the time-0 tree may take (0: not staged)
+hipError_t launch_finish(const DevScene& sc, const DevScene* scd, const RenderParams& rp, const PathState& st,
+                         const QView& in, uint32_t n, unsigned long long* seg_count, size_t tree0_budget,
+                         uint32_t depth, hipStream_t s);
+// bytes of LDS k_extend_lds needs for the scene's time-0 tree (0 = cannot run)
+size_t extend_lds_bytes(const DevScene& sc);
+// max_blocks: every block the kernel can keep on the device at once with `lds` bytes of dynamic LDS
+hipError_t extend_lds_prepare(const DevScene& sc, size_t lds, uint32_t* max_blocks);
+// LDS bytes k_camera needs (0 = cannot run)
+size_t camera_lds_bytes(const DevScene& sc);
+hipError_t camera_prepare(const DevScene& sc, size_t lds, uint32_t* max_blocks);
+// raygen + the depth-0 closest hit in one kernel; lds / max_blocks: camera_lds_bytes / camera_prepare;
+// err: the word a block sets when its LDS allocation was too small
+hipError_t launch_camera(const DevScene& sc, const RenderParams& rp, const PathState& st, uint32_t n,
+                         const HitBuf& hit, uint32_t shard_cap, uint32_t* counts, size_t lds, uint32_t max_blocks,
+                         unsigned long long* err, hipStream_t s);
+// a depth >= 1 extend with the time-0 tree in LDS; max_blocks: extend_lds_prepare's; err as above
+hipError_t launch_extend_lds(const DevScene& sc, const RenderParams& rp, const PathState& st, const QView& in,
+                             uint32_t n, const HitBuf& hit, uint32_t shard_cap, uint32_t* counts,
+                             uint32_t max_blocks, unsigned long long* err, hipStream_t s);
+bool curve_persistent();                    // the host's check before a fused launch
+// rt_curve_depth_probe: bez_maxd on ray-space control points (12 doubles per curve) and 8 eps
+hipError_t launch_curve_depth(const double* cps, const double* eps8, uint32_t n, int32_t* out, hipStream_t s);
+// rt_hit_rays: n rays of 7 doubles (origin, direction, time); the closest hit's t and material
+hipError_t launch_hit_rays(const DevScene& sc, const double* rays, uint32_t n, double* out_t, int32_t* out_mat,
+                           hipStream_t s);
+// the device fault word: read and clear
+hipError_t take_fault(uint32_t* out);
+// the batched-curve counters: read and clear
+hipError_t take_curve_stats(unsigned long long out[2]);
+// test hooks: the samplers' attempt cap and the persistent curve kernel's per-ray iteration cap (0 = the
+// scene's bound)
+hipError_t set_test_caps(int reject_cap, uint32_t curve_ray_cap);
+
+// --------------------------------------------------------- rt_frame.hip
+// S: the chunk's samples per pixel, added to accum in sample order
+hipError_t launch_accumulate(const RenderParams& rp, uint32_t S, double* accum, hipStream_t s);
+// launch_accumulate for a listed render, which also adds the samples' squares to accum2 and S to
+// count (each nullable)
+hipError_t launch_accumulate_moments(const RenderParams& rp, uint32_t S, double* accum, double* accum2,
+                                     uint32_t* count, hipStream_t s);
+// n: the accumulator's doubles (3 per pixel); count: the samples per pixel
+hipError_t launch_resolve_u8(const double* accum, uint32_t n, int count, uint8_t* out, hipStream_t s);
+// the resolve with each pixel's own sample count
+hipError_t launch_resolve_u8_counts(const double* accum, const uint32_t* count, uint32_t n, uint8_t* out,
+                                    hipStream_t s);
+// the frame-end gather's placement: shard pixel q's three sums to image pixel pix[q]
+hipError_t launch_scatter_pixels(const double* src, const uint32_t* pix, uint32_t n, double* frame, hipStream_t s);
+// blocks the selection of an n-entry list runs (its scratch is 3 words per block)
+uint32_t select_blocks(uint32_t n);
+// pix_in: null = entry i is pixel i; scratch: 3 * select_blocks(n) words; totals: two 64-bit words
+// {kept, capped}; pix_out: the kept entries in pix_in's order
+hipError_t launch_select(const uint32_t* pix_in, uint32_t n, const double* accum, const double* accum2,
+                         const uint32_t* count, double tol, double flr, uint32_t max_spp, uint32_t* scratch,
+                         unsigned long long* totals, uint32_t* pix_out, hipStream_t s);
+// a caller's pixel list, read only: its largest entry into *out_max
+hipError_t launch_check_pixels(const uint32_t* pix, uint32_t n, uint32_t* out_max, hipStream_t s);
+
+}  // namespace rtamd

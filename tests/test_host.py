@@ -212,7 +212,9 @@ def test_env_hooks_are_documented():
     curve extend's switches and RTAMD_FUSE_BATCH; RTAMD_DEBUG_DEPTH only in the RT_STATS build)."""
     csrc = os.path.join(ROOT, "scheme-raytrace_amd", "csrc")
     names = set()
-    for f in ("rt_api.cpp", "rt_kernels.hip"):
+    sources = [f for f in sorted(os.listdir(csrc)) if f.endswith((".cpp", ".hip", ".h"))]
+    assert "rt_render.cpp" in sources and "rt_kernels.hip" in sources and "rt_host.h" in sources
+    for f in sources:
         names |= set(re.findall(r'getenv\("(RTAMD_[A-Z0-9_]+)"\)', open(os.path.join(csrc, f)).read()))
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     sec = doc[doc.index("Test hooks that remain environment variables"):doc.index("Errors: every entry point")]

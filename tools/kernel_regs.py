@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel register / spill / LDS / scratch figures from the device
-assembly (make -C scheme-raytrace_amd/csrc asm -> rt_kernels.s).
-usage: python tools/kernel_regs.py [rt_kernels.s] [name-filter]"""
+assembly (make -C scheme-raytrace_amd/csrc asm -> rt_kernels.s, rt_frame.s).
+usage: python tools/kernel_regs.py [file.s ...] [name-filter]   (default: both files)"""
 import re
 import sys
 
@@ -23,9 +23,12 @@ def kernels(path):
 
 
 if __name__ == "__main__":
-    path = sys.argv[1] if len(sys.argv) > 1 else "scheme-raytrace_amd/csrc/rt_kernels.s"
-    flt = sys.argv[2] if len(sys.argv) > 2 else ""
-    for name, f in sorted(kernels(path).items()):
+    paths = [a for a in sys.argv[1:] if a.endswith(".s")]
+    flt = "".join([a for a in sys.argv[1:] if not a.endswith(".s")][:1])
+    found = {}
+    for path in paths or ["scheme-raytrace_amd/csrc/rt_kernels.s", "scheme-raytrace_amd/csrc/rt_frame.s"]:
+        found.update(kernels(path))
+    for name, f in sorted(found.items()):
         if flt in name:
             print("%-90s vgpr %3d agpr %3d spill %3d lds %6d scratch %4d" % (
                 name[:90], f.get("vgpr_count", 0), f.get("agpr_count", 0), f.get("vgpr_spill_count", 0),

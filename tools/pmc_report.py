@@ -160,6 +160,7 @@ def main():
     report["extend_phase"] = pmc_ext
     report["shade_phase"] = pmc_sh
     # stamp: bench.py uses these counters only while the kernels are the ones they were measured on
+    # (rt_kernels.hip alone, as bench.py checks: it holds every kernel these counters describe; rt_frame.hip's do not enter them)
     with open(os.path.join(ROOT, "scheme-raytrace_amd", "csrc", "rt_kernels.hip"), "rb") as f:
         sha = hashlib.sha256(f.read()).hexdigest()[:16]
     for rec in (report, pmc_ext, pmc_sh):
