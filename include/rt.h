@@ -426,6 +426,78 @@ int rt_resolve_u8_counts(const double* accum, const uint32_t* count, int nx, int
 int rt_resolve_u8_counts_device(int ctx, const double* accum_device, const uint32_t* count_device,
                                 int nx, int ny, uint8_t* out_device, void* stream);
 
+/* ---- first-hit feature buffers (an extension: what a denoiser or compositor reads beside the radiance) ---
+ * Opt-in: nothing above changes.  RT_ABI_VERSION stays 7; test RT_HAS_FEATURES for these entry points.
+ *
+ * Each pixel j = y*nx+x (y-up) has one record of RT_FEATURE_DOUBLES running sums, feat[8j+0..2] albedo rgb,
+ * [3..5] normal xyz, [6] t, [7] hits.  For every listed pixel and every pass s in [spp_begin,
+ * spp_begin+spp_count) the call takes the camera ray rt_render* traces for (seed, pixel, s) — the same
+ * draws in the same order: jitter u, jitter v, the unit-disk rejection loop, the time — and its closest hit
+ * in (0.001, 999999999999); a constant medium's hit test goes on drawing from the same stream, so the hit
+ * is the path's own first hit.  Each channel is added to the pixel's record in sample order, as accum is:
+ *   hit:   albedo += the first-hit material's texture value at the hit point, as the shading evaluates it
+ *          (lambertian / metal: the albedo texture; diffuse light: the emit texture, on either face; medium:
+ *          the phase texture; dielectric: (1, 1, 1));
+ *          normal += the hit record's normal as the scatter function receives it (after flip-normals and
+ *          the translate / rotate-y chain, not renormalised; curves: -dir; a medium: (1, 0, 0));
+ *          t += the hit record's t (curves: the distance along unit(dir), see rt_add_bezier); hits += 1.
+ *   miss:  albedo += the ray's sky colour (gradient or black); the other five channels += 0.
+ * pix_device (device memory, nullable = the whole frame) lists n unique pixels < nx*ny: the range is checked
+ * by a read-only pass over the list before anything is written (an entry >= nx*ny fails the call with feat
+ * untouched), pixels not listed are neither read nor written, and with n == 0 or spp_count == 0 the call
+ * does nothing.  Null feat, bad handles and negative arguments are refused before any device work.  Device
+ * faults (RT_FAULT_*) are reported as for renders.  rt_render_features: feat is a HOST buffer of nx*ny*8
+ * doubles, copied to the device and back (the whole frame).  Not available over tile shards. */
+#define RT_HAS_FEATURES 1
+#define RT_FEATURE_DOUBLES 8
+int rt_render_features_device(int scene, int nx, int ny, const uint32_t* pix_device /*nullable = whole frame*/, int64_t n,
+                              int spp_begin, int spp_count, uint64_t seed, double* feat_device, void* stream);
+int rt_render_features(int scene, int nx, int ny, int spp_begin, int spp_count, uint64_t seed, double* feat_host);
+
+/* ---- denoiser (an extension): an edge-avoiding a-trous filter guided by the feature buffers and by the
+ * variance of the mean that accum2 / count give — the spatial half of SVGF, with albedo demodulation.
+ * Test RT_HAS_DENOISE.  out_mean receives the filtered per-pixel MEAN radiance (nx*ny*3; resolve it with
+ * rt_resolve_u8(_device) and sample_count 1); it must not alias an input.  accum2 and count are nullable.
+ * All arithmetic is f64 in this operation order (the library is built without FMA contraction;
+ * rtamd.denoise.atrous is the NumPy restatement).
+ *
+ * Per pixel j, with n = (double)count[j] (count NULL: sample_count) and m = (double)feat_count:
+ *     c_k   = n == 0 ? 0 : S_k / n                      S = accum[3j+k], k = 0,1,2
+ *     a_k   = feat[8j+k] / m,  N = feat[8j+3..5] / m,  z = feat[8j+6] / m,  h = feat[8j+7] / m
+ *     den_k = a_k > albedo_floor ? a_k : albedo_floor
+ *     u_k   = c_k / den_k                               the demodulated signal
+ *     d_k   = Q_k - (S_k*S_k)/n                         Q = accum2[3j+k]
+ *     e_k   = ((d_k < 0 ? 0 : d_k) / (n*(n-1))) / (den_k*den_k)
+ *     v     = (e_0 + e_1) + e_2                         0 where n < 2 or accum2 is NULL
+ *     l     = (u_0 + u_1) + u_2
+ * A pixel is *valid* when u_0, u_1, u_2 and v are all finite.
+ * Iteration i = 0 .. iterations-1 has step s = 2^i.  For a valid pixel p = (x, y) the taps are q = (x + dx*s,
+ * y + dy*s), dy = -2..2 the outer loop, dx = -2..2 the inner one; taps outside the frame and taps that are
+ * not valid are skipped.  With k = [1/16, 1/4, 3/8, 1/4, 1/16] and hk = k[dy+2]*k[dx+2]:
+ *     centre tap: w = hk;  any other tap:
+ *     wn = 1 if h_p == 0 and h_q == 0, else g = (N_p.x*N_q.x + N_p.y*N_q.y) + N_p.z*N_q.z,
+ *          wn = g > 0 ? g : 0, then wn = wn*wn repeated normal_squarings times
+ *     zm = z_p > z_q ? z_p : z_q;   wz = exp(-(|z_p - z_q| / (sigma_z*zm + 1e-300)))
+ *     wl = exp(-(|l_p - l_q| / (sigma_l*sqrt(v_p) + 1e-10))),  1 when accum2 is NULL
+ *     w  = ((hk*wn)*wz)*wl
+ *     W += w;  U_k += w*u_q,k;  V += (w*w)*v_q           each sum from 0, in tap order
+ * then u'_k = U_k / W, v' = V / (W*W), and l is recomputed from u' for the next iteration.  A pixel that
+ * is not valid keeps its u and v through every iteration.  After the last one out_mean[3j+k] = u_k*den_k.
+ * Refused before any device work: iterations outside 1..12, normal_squarings > 16, sigma_z, sigma_l or
+ * albedo_floor not finite or <= 0, feat_count == 0, null pointers (accum, feat, out_mean, p), out_mean
+ * equal to an input, bad handles.  The filter's scratch (two signal buffers of 32 B and a guide buffer of
+ * 40 B per pixel) belongs to the context: sized at first use, freed by rt_context_destroy and
+ * rt_context_release_pools.  rt_denoise: the same with HOST buffers (PCIe-inclusive). */
+#define RT_HAS_DENOISE 1
+/* (a struct tag, not a typedef: the host entry point carries the same name) */
+struct rt_denoise { uint32_t iterations, normal_squarings; double sigma_z, sigma_l, albedo_floor; };
+int rt_denoise_device(int ctx, int nx, int ny, const struct rt_denoise* p,
+                      const double* accum, const double* accum2 /*nullable*/, const uint32_t* count /*nullable*/, uint32_t sample_count,
+                      const double* feat, uint32_t feat_count, double* out_mean /* nx*ny*3, may not alias the inputs */, void* stream);
+int rt_denoise(int ctx, int nx, int ny, const struct rt_denoise* p,
+               const double* accum, const double* accum2 /*nullable*/, const uint32_t* count /*nullable*/, uint32_t sample_count,
+               const double* feat, uint32_t feat_count, double* out_mean);
+
 #ifdef __cplusplus
 }
 #endif

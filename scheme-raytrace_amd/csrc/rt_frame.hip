@@ -12,6 +12,11 @@
 //   k_select_count / _scan / _scatter  stable compaction of the not-converged pixels of a list
 //   k_check_pixels        a caller's pixel list's largest entry (read only)
 //   k_resolve_u8_counts   k_resolve_u8 with each pixel's own sample count
+//
+// Denoiser (an extension, include/rt.h "denoiser"):
+//   k_denoise_prepare     per pixel: the guide record (normal, depth, hit fraction) and the demodulated
+//                         signal with the variance of its mean
+//   k_denoise_atrous<LAST> one a-trous iteration over ping-pong signal buffers; the last one remodulates
 #include <hip/hip_runtime.h>
 #include "rt_device.h"
 #include "rt_launch.h"
@@ -281,6 +286,150 @@ hipError_t launch_resolve_u8_counts(const double* accum, const uint32_t* count, 
     if (n == 0u) return hipSuccess;
     hipLaunchKernelGGL(k_resolve_u8_counts, dim3((n + 255u) / 256u), dim3(256), 0, s, accum, count, n, out);
     return hipGetLastError();
+}
+
+// =====================================================================
+// Denoiser (include/rt.h, "denoiser"): an edge-avoiding a-trous filter of the demodulated mean, guided
+// by the first-hit features and the variance of the mean.  Every expression below is the header's rule
+// in its operation order (rtamd.denoise.atrous restates it in NumPy); one lane per pixel, 16x16 blocks.
+// =====================================================================
+struct alignas(8) DnGuide { double nx, ny, nz, z, h; };          // 40 B
+struct alignas(16) DnSignal { double u0, u1, u2, v; };           // 32 B
+static_assert(sizeof(DnGuide) == kDenoiseGuideBytes && sizeof(DnSignal) == kDenoiseSignalBytes, "denoiser records");
+struct DnArgs {
+    uint32_t nx, ny;
+    const double* accum;
+    const double* accum2;          // nullable
+    const uint32_t* count;         // nullable: every pixel has sample_count samples
+    double sample_count, feat_count;
+    const double* feat;
+    double sigma_z, sigma_l, albedo_floor;
+    uint32_t normal_squarings;
+};
+// the B3-spline kernel [1/16, 1/4, 3/8, 1/4, 1/16] at offset d = -2..2 (exact binary fractions)
+__device__ __forceinline__ double dn_kernel(const int d) { return d == 0 ? 0.375 : (d == 1 || d == -1) ? 0.25 : 0.0625; }
+__device__ __forceinline__ bool dn_finite(const double x) { return fabs(x) < __builtin_inf(); }   // false for NaN
+__device__ __forceinline__ bool dn_valid(const DnSignal& s) {
+    return dn_finite(s.u0) && dn_finite(s.u1) && dn_finite(s.u2) && dn_finite(s.v);
+}
+__device__ __forceinline__ double dn_den(const DnArgs& a, const size_t j, const int k) {
+    const double al = a.feat[RT_FEATURE_DOUBLES * j + k] / a.feat_count;
+    return al > a.albedo_floor ? al : a.albedo_floor;
+}
+__global__ __launch_bounds__(256) void k_denoise_prepare(const DnArgs a, DnGuide* __restrict__ guide,
+                                                         DnSignal* __restrict__ sig) {
+#pragma clang fp contract(off)
+    const uint32_t x = blockIdx.x * 16u + (threadIdx.x & 15u), y = blockIdx.y * 16u + (threadIdx.x >> 4);
+    if (x >= a.nx || y >= a.ny) return;
+    const size_t j = (size_t)y * a.nx + x;
+    const double n = a.count ? (double)a.count[j] : a.sample_count;
+    const double m = a.feat_count;
+    const double* f = a.feat + RT_FEATURE_DOUBLES * j;
+    guide[j] = DnGuide{f[3] / m, f[4] / m, f[5] / m, f[6] / m, f[7] / m};
+    const double nn = n * (n - 1.0);
+    double u[3], v = 0.0;
+    double e[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < 3; ++k) {
+        const double S = a.accum[3u * j + k];
+        const double c = n == 0.0 ? 0.0 : S / n;
+        const double den = dn_den(a, j, k);
+        u[k] = c / den;
+        if (a.accum2 && n >= 2.0) {
+            const double d = a.accum2[3u * j + k] - (S * S) / n;
+            e[k] = ((d < 0.0 ? 0.0 : d) / nn) / (den * den);
+        }
+    }
+    if (a.accum2 && n >= 2.0) v = (e[0] + e[1]) + e[2];
+    sig[j] = DnSignal{u[0], u[1], u[2], v};
+}
+// One iteration at step `step`: taps (dx, dy) in {-2..2}^2 at (x + dx*step, y + dy*step), dy the outer loop.
+// Taps come straight from global memory: a pixel's 25 taps are 25 distinct 32-B + 40-B records whatever
+// the step, neighbouring lanes read neighbouring records, and the frame's records (72 B per pixel) stay in
+// the L2 / Infinity Cache between the taps' re-reads (DESIGN 4.6 has the measured time per iteration).
+// LAST: write u * den to out_mean instead of the signal record.
+template <bool LAST>
+__global__ __launch_bounds__(256) void k_denoise_atrous(const DnArgs a, const uint32_t step,
+                                                        const DnGuide* __restrict__ guide, const DnSignal* __restrict__ in,
+                                                        DnSignal* __restrict__ out, double* __restrict__ out_mean) {
+#pragma clang fp contract(off)
+    const uint32_t x = blockIdx.x * 16u + (threadIdx.x & 15u), y = blockIdx.y * 16u + (threadIdx.x >> 4);
+    if (x >= a.nx || y >= a.ny) return;
+    const size_t j = (size_t)y * a.nx + x;
+    const DnSignal sp = in[j];
+    DnSignal r = sp;                                       // a pixel that is not valid passes through
+    if (dn_valid(sp)) {
+        const DnGuide gp = guide[j];
+        const double lp = (sp.u0 + sp.u1) + sp.u2;
+        const double lden = a.sigma_l * sqrt(sp.v) + 1e-10;
+        double W = 0.0, U0 = 0.0, U1 = 0.0, U2 = 0.0, V = 0.0;
+        for (int dy = -2; dy <= 2; ++dy) {
+            const int64_t yy = (int64_t)y + (int64_t)dy * (int64_t)step;
+            if (yy < 0 || yy >= (int64_t)a.ny) continue;
+            for (int dx = -2; dx <= 2; ++dx) {
+                const int64_t xx = (int64_t)x + (int64_t)dx * (int64_t)step;
+                if (xx < 0 || xx >= (int64_t)a.nx) continue;
+                const double hk = dn_kernel(dy) * dn_kernel(dx);
+                double w;
+                DnSignal sq;
+                if (dx == 0 && dy == 0) {
+                    w = hk;
+                    sq = sp;
+                } else {
+                    const size_t jq = (size_t)yy * a.nx + (size_t)xx;
+                    sq = in[jq];
+                    if (!dn_valid(sq)) continue;
+                    const DnGuide gq = guide[jq];
+                    double wn = 1.0;
+                    if (!(gp.h == 0.0 && gq.h == 0.0)) {
+                        const double g = (gp.nx * gq.nx + gp.ny * gq.ny) + gp.nz * gq.nz;
+                        wn = g > 0.0 ? g : 0.0;
+                        for (uint32_t t = 0; t < a.normal_squarings; ++t) wn = wn * wn;
+                    }
+                    const double zm = gp.z > gq.z ? gp.z : gq.z;
+                    const double wz = exp(-(fabs(gp.z - gq.z) / (a.sigma_z * zm + 1e-300)));
+                    double wl = 1.0;
+                    if (a.accum2) {
+                        const double lq = (sq.u0 + sq.u1) + sq.u2;
+                        wl = exp(-(fabs(lp - lq) / lden));
+                    }
+                    w = ((hk * wn) * wz) * wl;
+                }
+                W = W + w;
+                U0 = U0 + w * sq.u0; U1 = U1 + w * sq.u1; U2 = U2 + w * sq.u2;
+                V = V + (w * w) * sq.v;
+            }
+        }
+        r = DnSignal{U0 / W, U1 / W, U2 / W, V / (W * W)};
+    }
+    if (LAST) {
+        out_mean[3u * j] = r.u0 * dn_den(a, j, 0);
+        out_mean[3u * j + 1] = r.u1 * dn_den(a, j, 1);
+        out_mean[3u * j + 2] = r.u2 * dn_den(a, j, 2);
+    } else {
+        out[j] = r;
+    }
+}
+hipError_t launch_denoise(int nx, int ny, const struct rt_denoise& p, const double* accum, const double* accum2,
+                          const uint32_t* count, uint32_t sample_count, const double* feat, uint32_t feat_count,
+                          void* guide, void* sig_a, void* sig_b, double* out_mean, hipStream_t s) {
+    const DnArgs a{(uint32_t)nx, (uint32_t)ny, accum, accum2, count, (double)sample_count, (double)feat_count, feat,
+                   p.sigma_z, p.sigma_l, p.albedo_floor, p.normal_squarings};
+    const dim3 grid(((uint32_t)nx + 15u) / 16u, ((uint32_t)ny + 15u) / 16u), block(256);
+    DnGuide* g = static_cast<DnGuide*>(guide);
+    DnSignal* cur = static_cast<DnSignal*>(sig_a);
+    DnSignal* nxt = static_cast<DnSignal*>(sig_b);
+    hipLaunchKernelGGL(k_denoise_prepare, grid, block, 0, s, a, g, cur);
+    HIP_RETURN_IF(hipGetLastError());
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        const uint32_t step = 1u << i;
+        if (i + 1u == p.iterations)
+            hipLaunchKernelGGL((k_denoise_atrous<true>), grid, block, 0, s, a, step, g, cur, nxt, out_mean);
+        else
+            hipLaunchKernelGGL((k_denoise_atrous<false>), grid, block, 0, s, a, step, g, cur, nxt, out_mean);
+        HIP_RETURN_IF(hipGetLastError());
+        DnSignal* t = cur; cur = nxt; nxt = t;
+    }
+    return hipSuccess;
 }
 
 }  // namespace rtamd

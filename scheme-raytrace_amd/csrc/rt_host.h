@@ -6,6 +6,8 @@
 //   rt_render.cpp    the render scheduler (render_impl) and the render / probe / resolve entry points
 //   rt_gather.cpp    the frame-end gather (RCCL and in-process)
 //   rt_adaptive.cpp  adaptive sampling
+//   rt_features.cpp  first-hit feature buffers
+//   rt_denoise.cpp   the variance-guided a-trous filter
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -139,6 +141,9 @@ struct Context {
     // counts / offsets and its two result words (with the range check's word after them), and the host
     // entry point's device copies of accum2 / count
     DevBuf sel_list[2], sel_scratch, sel_words, accum2_tmp, count_tmp;
+    // denoiser scratch: the ping-pong signal buffers (32 B per pixel each) and the guide buffer (40 B per pixel),
+    // sized at first use; rt_context_release_pools frees them
+    DevBuf dn_signal[2], dn_guide;
 };
 
 struct Scene {
@@ -261,5 +266,9 @@ struct PixSet {
 // rt_render.cpp: passes spp_begin .. spp_begin+spp_count-1 of the pixels of px into accum
 int render_impl(Scene* s, int nx, int ny, const PixSet& px, int spp_begin, int spp_count, uint64_t seed,
                 double* accum, hipStream_t stream);
+// rt_render.cpp: the pixels `ps` selects as a PixSet, the scene's cached device list (uploaded again when
+// the selection differs from the cached one); and rt_last_error's text for a device fault word
+int pixset_of(Scene* s, int nx, int ny, const PixSel& ps, bool compact, PixSet* out);
+std::string fault_text(uint32_t f);
 
 }  // namespace rtamd

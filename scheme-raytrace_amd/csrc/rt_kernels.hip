@@ -17,6 +17,10 @@
 //   k_finish<F> the depth tail: extend+shade looped  (same code; persistent lanes refill
 //               per lane for the last paths           from the remaining path list)
 //
+//   k_features<F,PN> first-hit feature buffers       (an extension, include/rt.h: camera ray +
+//               (albedo, normal, t, hits) of the      closest hit + hit record + texture, no bounce)
+//               camera samples a render takes
+//
 // (the frame-buffer kernels — accumulate, resolve, the gather's scatter, the adaptive selection — are
 // rt_frame.hip's)
 //
@@ -3058,6 +3062,90 @@ __global__ __launch_bounds__(256, (finish_waves<F, PN, LSM>())) void k_finish(co
     if (lane == 0u && segs) atomicAdd(tail_ctl, (unsigned long long)segs);
 }
 
+// =====================================================================
+// k_features<F, PN> — first-hit feature buffers (include/rt.h, "feature buffers"; an extension, no
+// counterpart in the reference).  One lane per listed pixel, in the list's (16x16-tile) order; the lane
+// loops over the call's passes and keeps its eight running sums in registers, so sample order is fixed
+// without atomics, and writes one 64-byte record.  Every pass takes the camera ray the render traces for
+// (seed, pixel, pass) — camera_ray, the same draws — and its closest hit with the generic closest_hit<F>
+// (a medium's hit test goes on drawing from the ray's stream, as k_extend's does at depth 0).
+// =====================================================================
+// The hit record as shade_hit forms it before the material's scatter: the point on the (instance-local)
+// ray and the normal, flipped and taken back out of the instance chain, not renormalised.  Restated here:
+// shade_hit's own copy is scheduled into every shade kernel's register budget.
+__device__ __forceinline__ void feature_hit(const DevScene& sc, const LeafInfo& li, const v3 o0, const v3 d0,
+                                            const double time, const double t, v3& pt, v3& nrm) {
+    v3 o = o0, d = d0;
+    if (li.chain >= 0) chain_ray(sc.chains[li.chain], o, d);
+    pt = o + d * t;
+    if (li.type == LEAF_SPHERE) {
+        nrm = (pt - mk(li.c[0], li.c[1], li.c[2])) * li.inv_r;
+    } else if (li.type == LEAF_MSPHERE) {
+        v3 cen;
+        if (__double_as_longlong(time) == 0ll) {
+            cen = mk(li.c[0], li.c[1], li.c[2]);
+        } else {
+            const MSphereRec S = sc.msph[li.local];
+            cen = mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * ((time - S.t0) / S.den);
+        }
+        nrm = (pt - cen) * li.inv_r;
+    } else if (li.type == LEAF_RECT_XY) {
+        nrm = mk(0.0, 0.0, 1.0);
+    } else if (li.type == LEAF_RECT_XZ) {
+        nrm = mk(0.0, 1.0, 0.0);
+    } else if (li.type == LEAF_RECT_YZ || li.type == LEAF_MEDIUM) {
+        nrm = mk(1.0, 0.0, 0.0);
+    } else if (li.type == LEAF_KLEIN) {
+        const KleinRec K = sc.klein[li.local];
+        nrm = klein_normal(mk(K.cx, K.cy, K.cz), pt);
+    } else {
+        nrm = d * -1.0;
+    }
+    if (li.flip) nrm = nrm * -1.0;
+    if (li.chain >= 0) chain_hit(sc.chains[li.chain], pt, nrm);
+}
+template <int F, bool PN>
+__global__ __launch_bounds__(256) void k_features(const DevScene sc, const RenderParams rp, const uint32_t S,
+                                                  double* __restrict__ feat) {
+    // dynamic LDS: the per-lane BVH stack (256 x sc.lane_stack words), then the Perlin tables (PN)
+    extern __shared__ uint32_t s_lstack[];
+    constexpr bool BEZ = (F & kFeatCurves) != 0;
+    __shared__ BezWave s_bw[BEZ ? 4 : 1];
+    const int LS = sc.lane_stack;
+    PerlinLds& P = *reinterpret_cast<PerlinLds*>(s_lstack + (size_t)256 * (size_t)(LS > 0 ? LS : 1));
+    stage_perlin<PN>(sc, P);
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+    if (q >= rp.npix) return;
+    double* rec = feat + (size_t)RT_FEATURE_DOUBLES * rp.pixlist[q];
+    double f0 = rec[0], f1 = rec[1], f2 = rec[2], f3 = rec[3], f4 = rec[4], f5 = rec[5], f6 = rec[6], f7 = rec[7];
+    RenderParams r1 = rp;                          // one pass at a time: work item q of pass spp0 + s
+    for (uint32_t s = 0; s < S; ++s) {
+        r1.spp0 = rp.spp0 + s;
+        v3 o, d;
+        double time, t;
+        Rng g;
+        camera_ray(sc, r1, q, o, d, time, g);
+        const int32_t leaf = closest_hit<F>(sc, o, d, time, t, s_lstack + threadIdx.x, LS,
+                                            &s_bw[BEZ ? (threadIdx.x >> 6) : 0], &g, tree0_hbm(sc), treeA_hbm(sc));
+        v3 a, n = mk(0.0, 0.0, 0.0);
+        double tt = 0.0, hit = 0.0;
+        if (leaf < 0) {
+            a = sky_radiance(sc, d);
+        } else {
+            const LeafInfo& li = sc.leaves[leaf];
+            v3 pt;
+            feature_hit(sc, li, o, d, time, t, pt, n);
+            a = li.mtype == MAT_DIELECTRIC ? mk(1.0, 1.0, 1.0) : leaf_tex<PN>(sc, P, li, pt);
+            tt = t;
+            hit = 1.0;
+        }
+        f0 = f0 + a.x; f1 = f1 + a.y; f2 = f2 + a.z;
+        f3 = f3 + n.x; f4 = f4 + n.y; f5 = f5 + n.z;
+        f6 = f6 + tt; f7 = f7 + hit;
+    }
+    rec[0] = f0; rec[1] = f1; rec[2] = f2; rec[3] = f3; rec[4] = f4; rec[5] = f5; rec[6] = f6; rec[7] = f7;
+}
+
 // ------------------------------------------------------------ launchers
 #define HIP_RETURN_IF(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 hipError_t launch_raygen(const DevScene& sc, const RenderParams& rp, const PathState& st,
@@ -3161,6 +3249,26 @@ hipError_t launch_hit_rays(const DevScene& sc, const double* rays, uint32_t n, d
                            out_mat);
         break;
     }
+    return hipGetLastError();
+}
+hipError_t launch_features(const DevScene& sc, const RenderParams& rp, uint32_t S, double* feat, hipStream_t s) {
+    const uint32_t blocks = (rp.npix + 255u) / 256u;
+    if (!blocks || !S) return hipSuccess;
+    const bool pn = sc.has_noise_tex != 0;
+    const size_t lds = (size_t)256 * (size_t)(sc.lane_stack > 0 ? sc.lane_stack : 1) * sizeof(uint32_t) +
+                       ((pn && sc.has_perlin) ? sizeof(PerlinLds) : 0);
+#define RT_FEATURES_F(F)                                                                                    \
+    do {                                                                                                    \
+        if (pn) hipLaunchKernelGGL((k_features<F, true>), dim3(blocks), dim3(256), lds, s, sc, rp, S, feat);  \
+        else hipLaunchKernelGGL((k_features<F, false>), dim3(blocks), dim3(256), lds, s, sc, rp, S, feat);    \
+    } while (0)
+    switch (scene_features(sc)) {
+    case 0: RT_FEATURES_F(0); break;
+    case 1: RT_FEATURES_F(1); break;
+    case 2: RT_FEATURES_F(2); break;
+    default: RT_FEATURES_F(3); break;
+    }
+#undef RT_FEATURES_F
     return hipGetLastError();
 }
 // bytes of LDS k_extend_lds needs for the scene's time-0 tree (0 = cannot run)

@@ -52,6 +52,10 @@ hipError_t launch_curve_depth(const double* cps, const double* eps8, uint32_t n,
 // rt_hit_rays: n rays of 7 doubles (origin, direction, time); the closest hit's t and material
 hipError_t launch_hit_rays(const DevScene& sc, const double* rays, uint32_t n, double* out_t, int32_t* out_mat,
                            hipStream_t s);
+// rt_render_features: passes rp.spp0 .. rp.spp0 + S - 1 of the rp.npix pixels of rp.pixlist, their first-hit
+// features added to feat (RT_FEATURE_DOUBLES running sums per image pixel); only nx, ny, inx, iny, npix,
+// spp0, k0, k1 and pixlist of rp are read
+hipError_t launch_features(const DevScene& sc, const RenderParams& rp, uint32_t S, double* feat, hipStream_t s);
 // the device fault word: read and clear
 hipError_t take_fault(uint32_t* out);
 // the batched-curve counters: read and clear
@@ -83,5 +87,12 @@ hipError_t launch_select(const uint32_t* pix_in, uint32_t n, const double* accum
                          unsigned long long* totals, uint32_t* pix_out, hipStream_t s);
 // a caller's pixel list, read only: its largest entry into *out_max
 hipError_t launch_check_pixels(const uint32_t* pix, uint32_t n, uint32_t* out_max, hipStream_t s);
+// rt_denoise: the variance-guided a-trous filter of include/rt.h.  accum2 / count nullable (count null: every
+// pixel has sample_count samples); guide: npx 40-byte records, sig_a / sig_b: npx 32-byte records each
+// (the context's scratch); out_mean: npx * 3 doubles
+constexpr size_t kDenoiseGuideBytes = 40, kDenoiseSignalBytes = 32;
+hipError_t launch_denoise(int nx, int ny, const struct rt_denoise& p, const double* accum, const double* accum2,
+                          const uint32_t* count, uint32_t sample_count, const double* feat, uint32_t feat_count,
+                          void* guide, void* sig_a, void* sig_b, double* out_mean, hipStream_t s);
 
 }  // namespace rtamd

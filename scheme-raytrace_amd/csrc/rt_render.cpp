@@ -48,7 +48,7 @@ std::vector<uint32_t> make_pixlist(int nx, int ny, const PixSel& ps) {
 }
 }  // namespace rtamd
 
-namespace {
+namespace rtamd {
 std::string fault_text(uint32_t f) {
     std::string m = "device fault (flags " + std::to_string(f) + "):";
     if (f & RT_FAULT_REJECT) m += " a rejection sampler exceeded its attempt cap;";
@@ -58,7 +58,9 @@ std::string fault_text(uint32_t f) {
     if (f & RT_FAULT_LDS) m += " a persistent kernel's LDS allocation was too small;";
     return m;
 }
+}  // namespace rtamd
 
+namespace {
 // Path-pool cap (paths per chunk).  Bigger pools mean fewer chunks, each
 // with its own narrow tail: C2 (1920x1080x1024 spp) 13 383 Mrays/s with 96M
 // paths (22 chunks), 13 675 with 200M (12), 13 742 with 330M (8 chunks;
@@ -492,7 +494,7 @@ int render_impl(Scene* s, int nx, int ny, const PixSet& px, int spp_begin, int s
 }
 }  // namespace rtamd
 
-namespace {
+namespace rtamd {
 // The pixels `ps` selects as a PixSet: the scene's cached device list, made and uploaded again when the
 // selection differs from the cached one.  (nx, ny and ps are valid: render_sel)
 int pixset_of(Scene* s, int nx, int ny, const PixSel& ps, bool compact, PixSet* out) {
@@ -511,6 +513,9 @@ int pixset_of(Scene* s, int nx, int ny, const PixSel& ps, bool compact, PixSet* 
     *out = PixSet{s->pixlist.as<const uint32_t>(), s->pix_n, compact, nullptr, nullptr};
     return 0;
 }
+}  // namespace rtamd
+
+namespace {
 // render_impl over the pixels `ps` selects.  The checks stand in the order their errors have always won:
 // render_impl's first four, the selection's, the frame size.  A render of no passes does no list work
 // and leaves the cached list as it is (render_impl returns after its clears).

@@ -69,6 +69,8 @@ int rt_context_release_pools(int ctx) {
         if (L && L->stream) HIPCHK(hipStreamSynchronize(L->stream));
     for (auto& L : c->lanes) L.reset();
     c->pool_cap = 0;                               // the next render sizes them again
+    for (DevBuf& b : c->dn_signal) b.release();   // the denoiser's scratch (sized again at its next use)
+    c->dn_guide.release();
     return 0;
 }
 

@@ -73,6 +73,15 @@ class RtAdaptiveResult(ctypes.Structure):
                 ("ms_total", ctypes.c_double), ("ms_select", ctypes.c_double)]
 
 
+RT_FEATURE_DOUBLES = 8
+
+
+class RtDenoise(ctypes.Structure):
+    """struct rt_denoise: the a-trous filter's iterations and edge-stopping parameters."""
+    _fields_ = [("iterations", ctypes.c_uint32), ("normal_squarings", ctypes.c_uint32), ("sigma_z", ctypes.c_double),
+                ("sigma_l", ctypes.c_double), ("albedo_floor", ctypes.c_double)]
+
+
 # name -> argtypes (restype is always c_int status, except where noted)
 _SIGNATURES = {
     "rt_abi_version": [],
@@ -164,6 +173,17 @@ _SIGNATURES = {
     "rt_resolve_u8_counts": [_c_double_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.c_int, _c_u8_p],
     "rt_resolve_u8_counts_device": [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_void_p, ctypes.c_void_p],
+    # first-hit feature buffers (RT_HAS_FEATURES)
+    "rt_render_features_device": [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                  ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p],
+    "rt_render_features": [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                           _c_double_p],
+    # denoiser (RT_HAS_DENOISE)
+    "rt_denoise_device": [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RtDenoise), ctypes.c_void_p,
+                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                          ctypes.c_void_p, ctypes.c_void_p],
+    "rt_denoise": [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RtDenoise), _c_double_p, _c_double_p,
+                   ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, _c_double_p, ctypes.c_uint32, _c_double_p],
 }
 
 #: every symbol include/rt.h declares (tests check the .so exports all of them)

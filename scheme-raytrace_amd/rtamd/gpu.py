@@ -372,6 +372,62 @@ def resolve_u8_counts_device(accum_ptr, count_ptr, nx, ny, out_ptr, stream=None,
          ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0))
 
 
+def render_features_device(scene, nx, ny, spp_begin, spp_count, seed, feat_ptr, pix_ptr=None, n=0, stream=None,
+                           ctx=None):
+    """rt_render_features_device: the first-hit features (albedo, normal, t, hits: 8 running sums per pixel)
+    of passes [spp_begin, spp_begin+spp_count) added to the nx*ny*8 doubles at device pointer feat_ptr, for
+    the whole frame or the n pixels listed at device pointer pix_ptr (uint32, unique, < nx*ny)."""
+    h = upload(scene, ctx)
+    call("rt_render_features_device", h, nx, ny, ctypes.c_void_p(pix_ptr or 0), int(n), spp_begin, spp_count, _u64(seed),
+         ctypes.c_void_p(feat_ptr), ctypes.c_void_p(stream or 0))
+    return h
+
+
+def render_features_host(scene, nx, ny, spp_begin, spp_count, seed, feat, ctx=None):
+    """rt_render_features: as render_features_device on a host float64 array of nx*ny*8 (updated in place)."""
+    h = upload(scene, ctx)
+    if feat.dtype != np.float64 or not feat.flags.c_contiguous or feat.size != nx * ny * _lib.RT_FEATURE_DOUBLES:
+        raise ValueError("feat must be a contiguous float64 array of nx*ny*8 elements")
+    call("rt_render_features", h, nx, ny, spp_begin, spp_count, _u64(seed),
+         feat.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    return h
+
+
+def denoise_params(iterations=5, normal_squarings=7, sigma_z=0.1, sigma_l=4.0, albedo_floor=1e-2):
+    """A struct rt_denoise (include/rt.h, "denoiser") at the defaults of rtamd.denoise.DEFAULTS."""
+    return _lib.RtDenoise(int(iterations), int(normal_squarings), float(sigma_z), float(sigma_l), float(albedo_floor))
+
+
+def denoise_device(nx, ny, params, accum_ptr, accum2_ptr, count_ptr, sample_count, feat_ptr, feat_count, out_ptr,
+                   stream=None, ctx=None):
+    """rt_denoise_device: the filtered per-pixel mean radiance (nx*ny*3 doubles at out_ptr) of the sums at
+    accum_ptr, guided by the feature sums at feat_ptr (feat_count passes) and, where accum2_ptr is given, by
+    the variance of the mean; count_ptr None: every pixel has sample_count samples."""
+    ctx = ctx or default_context()
+    call("rt_denoise_device", ctx.handle, nx, ny, ctypes.byref(params), ctypes.c_void_p(accum_ptr),
+         ctypes.c_void_p(accum2_ptr or 0), ctypes.c_void_p(count_ptr or 0), int(sample_count), ctypes.c_void_p(feat_ptr),
+         int(feat_count), ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream or 0))
+
+
+def denoise_host(nx, ny, params, accum, accum2, count, sample_count, feat, feat_count, ctx=None):
+    """rt_denoise on host arrays (accum2 and count may be None); returns the filtered mean, nx*ny*3 float64."""
+    ctx = ctx or default_context()
+    dp, up = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint32)
+    a = np.ascontiguousarray(accum, dtype=np.float64).ravel()
+    f = np.ascontiguousarray(feat, dtype=np.float64).ravel()
+    if a.size != nx * ny * 3 or f.size != nx * ny * _lib.RT_FEATURE_DOUBLES:
+        raise ValueError("accum must have nx*ny*3 elements and feat nx*ny*8")
+    a2 = None if accum2 is None else np.ascontiguousarray(accum2, dtype=np.float64).ravel()
+    c = None if count is None else np.ascontiguousarray(count, dtype=np.uint32).ravel()
+    if (a2 is not None and a2.size != a.size) or (c is not None and c.size != nx * ny):
+        raise ValueError("accum2 must have nx*ny*3 elements and count nx*ny")
+    out = np.zeros(nx * ny * 3)
+    call("rt_denoise", ctx.handle, nx, ny, ctypes.byref(params), a.ctypes.data_as(dp),
+         a2.ctypes.data_as(dp) if a2 is not None else None, c.ctypes.data_as(up) if c is not None else None,
+         int(sample_count), f.ctypes.data_as(dp), int(feat_count), out.ctypes.data_as(dp))
+    return out
+
+
 def curve_depth_probe(cps, eps8, ctx=None):
     """rt_curve_depth_probe: the curve kernels' depth estimate (bez_maxd) for ray-space control points
     cps (n, 12) and 8 eps (n,); returns int32 depths."""

@@ -10,10 +10,14 @@ display step (main.scm:533-544: one row per call, then the next pass).
 ``render(scene, spp)`` runs many passes in one GPU call (same result as spp
 successive trace_all calls).  ``render_adaptive(scene, tol, ...)`` is an
 extension: passes per pixel until its estimated error is below ``tol``.
+``render_features(scene, spp)`` and ``denoise(**params)`` are extensions too:
+the first-hit feature buffers of the camera samples, and the variance-guided
+a-trous filter of the running sums they guide (include/rt.h, "denoiser").
 """
 import numpy as np
 
 from . import gpu
+from .denoise import DEFAULTS as DENOISE_DEFAULTS
 
 DEFAULT_SEED = 0x5EED0002
 
@@ -28,6 +32,11 @@ class Renderer:
         # render_adaptive only: the running sums of the samples' squares and each pixel's sample count
         self.raw_data2 = np.zeros(self.size_x * self.size_y * 3, dtype=np.float64)
         self.counts = np.zeros(self.size_x * self.size_y, dtype=np.uint32)
+        self.adaptive = False         # raw_data2 / counts hold the last render's moments (render_adaptive)
+        # render_features: the running sums of the first-hit features (albedo 3, normal 3, t, hits per pixel)
+        self.features = np.zeros(self.size_x * self.size_y * 8, dtype=np.float64)
+        self.feature_count = 0
+        self.denoised = None          # denoise(): the filtered mean radiance, nx*ny*3
         self.sample_count = 0
         self.current_y = 0            # *current-y* (main.scm:431)
         self.anim_sample_count = 1    # *sample-count* (main.scm:531)
@@ -69,6 +78,7 @@ class Renderer:
         if spp_begin is None:
             spp_begin = self.sample_count
         gpu.render_host(scene, self.size_x, self.size_y, spp_begin, spp, self.seed, self.raw_data, self.ctx)
+        self.adaptive = False         # raw_data2 / counts no longer describe raw_data
         self.sample_count = spp_begin + spp
         self.image = gpu.resolve_u8(self.raw_data, self.size_x, self.size_y, self.sample_count)
         return self.image
@@ -85,7 +95,69 @@ class Renderer:
             scene, self.size_x, self.size_y, p, self.seed, self.ctx)
         self.image = gpu.resolve_u8_counts(self.raw_data, self.counts, self.size_x, self.size_y)
         self.sample_count = int(self.counts.max())
+        self.adaptive = True
         return res
+
+    def render_features(self, scene, spp, spp_begin=None):
+        """The first-hit features of passes spp_begin+1 .. spp_begin+spp (default: continue after the
+        feature passes already taken) added to ``features``: the camera samples render() takes for the
+        same passes.  Views: albedo, normal, depth, hit_fraction."""
+        if spp_begin is None:
+            spp_begin = self.feature_count
+        gpu.render_features_host(scene, self.size_x, self.size_y, spp_begin, spp, self.seed, self.features, self.ctx)
+        self.feature_count = spp_begin + spp
+        return self.features
+
+    def _feature_mean(self, lo, hi):
+        if self.feature_count < 1:
+            raise ValueError("no feature passes yet (render_features)")
+        f = self.features.reshape(self.size_y, self.size_x, 8)[..., lo:hi] / float(self.feature_count)
+        return f[..., 0] if hi - lo == 1 else f
+
+    @property
+    def albedo(self):
+        """(ny, nx, 3), y-up: the mean first-hit texture value (the sky colour where the ray misses)."""
+        return self._feature_mean(0, 3)
+
+    @property
+    def normal(self):
+        """(ny, nx, 3): the mean first-hit normal (not renormalised; 0 for a miss)."""
+        return self._feature_mean(3, 6)
+
+    @property
+    def depth(self):
+        """(ny, nx): the mean first-hit t (0 for a miss)."""
+        return self._feature_mean(6, 7)
+
+    @property
+    def hit_fraction(self):
+        """(ny, nx): the fraction of the feature passes whose camera ray hit something."""
+        return self._feature_mean(7, 8)
+
+    def denoise(self, **params):
+        """The variance-guided a-trous filter (rt_denoise) of raw_data, guided by ``features``; the moments
+        raw_data2 / counts are used when an adaptive render filled them.  params: iterations,
+        normal_squarings, sigma_z, sigma_l, albedo_floor (rtamd.denoise.DEFAULTS).  Fills ``denoised``
+        (the filtered mean radiance, nx*ny*3) and returns it."""
+        if self.feature_count < 1:
+            raise ValueError("no feature passes yet (render_features)")
+        if self.sample_count < 1:
+            raise ValueError("nothing rendered yet")
+        p = gpu.denoise_params(**dict(DENOISE_DEFAULTS, **params))
+        self.denoised = gpu.denoise_host(self.size_x, self.size_y, p, self.raw_data,
+                                         self.raw_data2 if self.adaptive else None,
+                                         self.counts if self.adaptive else None, self.sample_count, self.features,
+                                         self.feature_count, self.ctx)
+        return self.denoised
+
+    def denoised_image(self):
+        """``denoised`` resolved like the image (sqrt, 8 bits)."""
+        if self.denoised is None:
+            raise ValueError("no denoised frame yet (denoise)")
+        return gpu.resolve_u8(self.denoised, self.size_x, self.size_y, 1)
+
+    def save_denoised_as_ppm(self, path="denoised.ppm"):
+        write_ppm(path, self.denoised_image(), self.size_x, self.size_y)
 
     def save_as_ppm(self, path="test.ppm"):
         """main.scm:439-450 — P3, rows written top-down (flipping y-up rows)."""
