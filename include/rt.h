@@ -286,6 +286,19 @@ enum { RT_FAULT_REJECT = 1, RT_FAULT_CURVE = 2, RT_FAULT_PATH = 4, RT_FAULT_SHAR
  * medium's hit test draws from the path's random stream. */
 int rt_hit_rays(int scene, int n, const double* rays, double* out_t, int32_t* out_mat);
 
+/* rt_hit_rays through a chosen closest-hit walk (a test probe: the renders pick their walks themselves).
+ * RT_WALK_HBM: the trees in device memory, 32-bit traversal stacks (rt_hit_rays is this walk).
+ * RT_WALK_LDS_TIME0: k_extend_lds's query, which every scattered ray takes in scenes whose time-0 tree
+ *   runs from LDS: that tree staged in LDS, 16-bit stacks, sign-selected slabs, leafless when the world is
+ *   one BVH (rt_scene_info.bvh_solo).  Every ray's time must be +0.0 bit for bit (the kernel never sees
+ *   another); refused when rt_scene_info.extend_lds_bytes is 0.
+ * RT_WALK_LDS_CAMERA: k_camera's query, which camera rays take: the all-times tree in LDS when the scene
+ *   has moving spheres (rt_scene_info.tree0_any_time 0), else the time-0 tree; the ray's own time; refused
+ *   when rt_scene_info.camera_lds_bytes is 0.
+ * Rays, outputs and the refusal of scenes with media as rt_hit_rays. */
+enum { RT_WALK_HBM = 0, RT_WALK_LDS_TIME0 = 1, RT_WALK_LDS_CAMERA = 2 };
+int rt_hit_rays_walk(int scene, int walk, int n, const double* rays, double* out_t, int32_t* out_mat);
+
 /* converge's subdivision depth (bezier.scm:179-193) as the curve kernels compute it (bez_maxd): for n
  * curves given in ray space (cps = n x 12 doubles, the control points after bezier-transform) and 8 eps
  * each (eps = width / 20), out_depth[i] = ceiling((log z) / (log 4)) with z = sqrt(2) n (n-1) l0 / (8 eps),
@@ -334,7 +347,7 @@ typedef struct rt_scene_info {
     double   commit_upload_ms; /* of it: device allocations and host-to-device copies */
     double   commit_sah_ms;   /* of it: the SAH builds of the world BVH (on commit_threads host threads) */
     int32_t  commit_threads;  /* host threads the SAH builds may use (the process's CPUs, at most 16) */
-    int32_t  reserved0;
+    int32_t  tree0_any_time;  /* 1: no moving spheres in the world BVH, so its time-0 tree serves rays of every time (was reserved0) */
 } rt_scene_info;
 int rt_get_scene_info(int scene, rt_scene_info* out);
 /* Record per-kernel HIP events during renders (adds a little host overhead). */

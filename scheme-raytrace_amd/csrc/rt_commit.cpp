@@ -329,6 +329,8 @@ int commit_scene(Scene* s, int world) {
       }
     });
     COMMIT_MARK("refs");
+    // list position -> (type, index in the type's array) of every world leaf (DevScene::order)
+    std::vector<int32_t> ord_type(f.leaves.size(), -1), ord_local(f.leaves.size(), -1);
     const bool use_bvh = !refs.empty() && refs.size() >= bvh_min_prims();
     std::vector<BvhNode> bvh_nodes;
     HostVec<BvhNode2> bvh2;
@@ -428,6 +430,8 @@ int commit_scene(Scene* s, int world) {
                     bez[(size_t)nb[i]].order = (uint32_t)r.leaf;      // the flattened list position
                     lbez[(size_t)nb[i]] = li;
                 }
+                ord_type[(size_t)r.leaf] = r.type;
+                ord_local[(size_t)r.leaf] = li.local;
             }
         });
         // Time-0 BVH.  Every scattered ray has time 0 (make-ray, ray.scm:8-9,
@@ -539,6 +543,11 @@ int commit_scene(Scene* s, int world) {
             r.a0 = o.a0; r.a1 = o.a1; r.b0 = o.b0; r.b1 = o.b1; r.k = o.k;
             li->local = (int)rect.size(); lrect[L.type - LEAF_RECT_XY].push_back(*li);
             rect.push_back(r);
+        }
+        if (li_world) {                                 // a world leaf: L is an element of f.leaves
+            const size_t at = (size_t)(&L - f.leaves.data());
+            ord_type[at] = L.type;
+            ord_local[at] = li->local;
         }
     };
     auto type_size = [&](int type) {
@@ -736,6 +745,17 @@ int commit_scene(Scene* s, int world) {
         std::vector<uint8_t> lc((leaves.size() + 15) / 16 * 16 + 16, 0);
         for (size_t k = 0; k < leaves.size(); ++k) lc[k] = (uint8_t)leaves[k].mtype;
         if (int rc = upload(s->d_leaf_cls, lc, &d.leaf_cls)) return rc;
+    }
+    {   // the world's leaf ids in list order (list_closest); none for scenes with media, which keep the grouped scan
+        std::vector<int32_t> order;
+        if (med.empty()) {
+            order.reserve(f.leaves.size());
+            for (size_t i = 0; i < f.leaves.size(); ++i)
+                if (ord_type[i] >= 0) order.push_back(base[ord_type[i]] + ord_local[i]);
+            if (order.size() != leaves.size()) return fail("internal: list order and leaf records out of step");
+        }
+        if (int rc = upload(s->d_order, order, &d.order)) return rc;
+        d.n_order = (int32_t)order.size();
     }
     if (int rc = upload(s->d_mats, s->mats, &d.mats)) return rc;
     if (int rc = upload(s->d_texs, s->texs, &d.texs)) return rc;

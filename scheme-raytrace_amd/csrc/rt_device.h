@@ -196,6 +196,9 @@ struct DevScene {
     int32_t mat_mask;                          // bit t set <=> some material of type t exists
     DevCamera cam;
     DevLight light;
+    // the world's leaf ids in list order (hit-obj-list's order; 0 entries in scenes with media): what a ray
+    // that lies in a rect's plane is scanned in (list_closest)
+    const int32_t* order;  int32_t n_order;
 };
 
 // Wavefront path state, SoA, one slot per live path (ping-pong buffers).

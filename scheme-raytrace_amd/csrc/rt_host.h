@@ -167,6 +167,7 @@ struct Scene {
     DevBuf d_bvh4, d_stk_ovf, d_bez_ring, d_fuse_ring;         // curve trees: BVH4, the walk's stack overflow, rings
     DevBuf d_dev;                                  // a device copy of `dev` (kernels that take the scene by pointer)
     DevBuf d_leaf_cls;
+    DevBuf d_order;
     size_t ext_lds = 0;                            // k_extend_lds: LDS bytes (0 = not used) and grid cap
     uint32_t ext_lds_blocks = 0;
     size_t cam_lds = 0;                            // k_camera (fused raygen + depth-0 extend), same

@@ -1552,7 +1552,8 @@ __device__ __forceinline__ TreeA treeA_hbm(const DevScene& sc) { return TreeA{sc
 // list order against the shrinking closest.
 template <int F>
 __device__ __forceinline__ void group_closest(const DevScene& sc, const Group& G, const v3 o0, const v3 d0,
-                                              const double time, double& closest, int32_t& best, Rng* rng) {
+                                              const double time, double& closest, int32_t& best, Rng* rng,
+                                              bool* nan_t = nullptr) {
     constexpr bool BEZ = (F & kFeatCurves) != 0;
     constexpr bool MED = (F & kFeatExtra) != 0;
     v3 o = o0, d = d0;
@@ -1609,10 +1610,68 @@ __device__ __forceinline__ void group_closest(const DevScene& sc, const Group& G
         for (int s = G.begin; s < G.end; ++s) {
             const RectRec R = sc.rect[s];
             const double t = (R.k - ok) / dk;
+            if (nan_t && t != t) *nan_t = true;             // the ray lies in the rect's plane: list_closest
             if (t < kTmin || t > closest) continue;
             const double A = oa + t * da, Bv = ob + t * db;
             if (A < R.a0 || A > R.a1 || Bv < R.b0 || Bv > R.b1) continue;
             closest = t; best = base + s;
+        }
+    }
+}
+
+// hit-obj-list as written (geometry.scm:33-50): the world's leaves one after the other in list order
+// (DevScene::order), no tree and no groups.  For the rays whose closest hit depends on that order: a rect
+// whose t is NaN (the ray lies in its plane, 0/0) passes both comparisons (Q20), becomes the closest hit
+// whatever came before, and lets every later rect in bounds pass `t > closest` — so the grouped scan above,
+// which meets the leaves by (chain, type), can end on another object.  Each leaf's test is the one the
+// groups and the tree walks run (the same operations on the same records).  Scenes with media keep the
+// grouped scan (their hit test draws random numbers; n_order is 0).
+template <int F>
+__device__ __forceinline__ void list_closest(const DevScene& sc, const v3 o0, const v3 d0, const double time,
+                                             double& closest, int32_t& best) {
+    constexpr bool BEZ = (F & kFeatCurves) != 0;
+    constexpr bool MED = (F & kFeatExtra) != 0;
+    closest = kTmax;
+    best = -1;
+    for (int k = 0; k < sc.n_order; ++k) {
+        const int32_t id = sc.order[k];
+        const int4 L = *reinterpret_cast<const int4*>(&sc.leaves[id]);      // type, chain, local, flip
+        const int32_t type = L.x, s = L.z;
+        v3 o = o0, d = d0;
+        if (L.y >= 0) chain_ray(sc.chains[L.y], o, d);
+        if (type == LEAF_SPHERE) {
+            const double a = dot(d, d), ia = 1.0 / a;
+            const SphereRec S = sc.sph[s];
+            sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, id, closest, best);
+        } else if (type == LEAF_MSPHERE) {
+            const double a = dot(d, d), ia = 1.0 / a;
+            const MSphereRec S = sc.msph[s];
+            const double frac = (time - S.t0) / S.den;
+            const v3 cen = mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * frac;
+            sphere_test(o, d, a, ia, cen, S.rr, id, closest, best);
+        } else if (type == LEAF_KLEIN) {
+            if (MED) {
+                double t;
+                if (klein_test(sc.klein[s], o, d, closest, t)) { closest = t; best = id; }
+            }
+        } else if (type == LEAF_BEZIER) {
+            if (BEZ) {
+                BezRay R;
+                bez_ray(o, d, R);
+                double t;
+                if (bezier_test(sc.bez[s], R, closest, t)) { closest = t; best = id; }
+            }
+        } else if (type != LEAF_MEDIUM) {
+            double ok, dk, oa, da, ob, db;
+            if (type == LEAF_RECT_XY) { ok = o.z; dk = d.z; oa = o.x; da = d.x; ob = o.y; db = d.y; }
+            else if (type == LEAF_RECT_XZ) { ok = o.y; dk = d.y; oa = o.x; da = d.x; ob = o.z; db = d.z; }
+            else { ok = o.x; dk = d.x; oa = o.y; da = d.y; ob = o.z; db = d.z; }
+            const RectRec R = sc.rect[s];
+            const double t = (R.k - ok) / dk;
+            if (t < kTmin || t > closest) continue;
+            const double A = oa + t * da, Bv = ob + t * db;
+            if (A < R.a0 || A > R.a1 || Bv < R.b0 || Bv > R.b1) continue;
+            closest = t; best = id;
         }
     }
 }
@@ -1624,6 +1683,7 @@ __device__ __forceinline__ int32_t closest_hit(const DevScene& sc, const v3 o0, 
                                                const TreeA ta) {
     constexpr bool BEZ = (F & kFeatCurves) != 0;
     int32_t best = -1;
+    bool nan_t = false;
     closest = kTmax;
     for (int g = 0; g < sc.n_groups; ++g) {
         const Group G = sc.groups[g];
@@ -1637,8 +1697,9 @@ __device__ __forceinline__ int32_t closest_hit(const DevScene& sc, const v3 o0, 
                                                      nullptr, ta.sph, ta.msph);
             continue;
         }
-        group_closest<F>(sc, G, o0, d0, time, closest, best, rng);
+        group_closest<F>(sc, G, o0, d0, time, closest, best, rng, &nan_t);
     }
+    if (nan_t && sc.n_order > 0) list_closest<F>(sc, o0, d0, time, closest, best);   // the list's order decides
     return best;
 }
 
@@ -2078,7 +2139,10 @@ __global__ __launch_bounds__(256, RT_CURVE_WAVES) void k_extend_curves(const Dev
                     int32_t leaf = (int32_t)(h.leaf_dep & ((1u << kFuseLeafBits) - 1u)) - 1;
                     PathRegs p;
                     load_path(st, h.slot, p, rp, h.leaf_dep >> kFuseLeafBits);
-                    for (int g = gb + 1; g < sc.n_groups; ++g) group_closest<0>(sc, sc.groups[g], p.o, p.d, p.time, t, leaf, nullptr);
+                    bool nan_t = false;
+                    for (int g = gb + 1; g < sc.n_groups; ++g)
+                        group_closest<0>(sc, sc.groups[g], p.o, p.d, p.time, t, leaf, nullptr, &nan_t);
+                    if (nan_t && sc.n_order > 0) list_closest<kFeatCurves>(sc, p.o, p.d, p.time, t, leaf);
                     v3 L;
                     if (leaf < 0) L = sky_radiance(sc, p.d);
                     else go = fused_shade<FUSE == 2>(sc, rp, p, t, leaf, L);
@@ -2105,7 +2169,10 @@ __global__ __launch_bounds__(256, RT_CURVE_WAVES) void k_extend_curves(const Dev
                 v3 o, d;
                 double tm;
                 ray_of(o, d, tm);
-                for (int g = gb + 1; g < sc.n_groups; ++g) group_closest<0>(sc, sc.groups[g], o, d, tm, closest, best, nullptr);
+                bool nan_t = false;
+                for (int g = gb + 1; g < sc.n_groups; ++g)
+                    group_closest<0>(sc, sc.groups[g], o, d, tm, closest, best, nullptr, &nan_t);
+                if (nan_t && sc.n_order > 0) list_closest<kFeatCurves>(sc, o, d, tm, closest, best);
                 if (gb + 1 < sc.n_groups && best >= 0) bcls = sc.leaf_cls[best];
                 if (best < 0) {
                     const v3 L = sky_radiance(sc, d);
@@ -2532,6 +2599,61 @@ __global__ __launch_bounds__(kExtLdsBlock, RT_CAMERA_WAVES) void k_camera(const 
         }
         const uint32_t slot = ext_append(cls, counts, shard_cap, s_cnt);
         if (cls >= 0 && slot != kNoSlot) hit.h[(size_t)cls * hit.stride + slot] = hr;
+    }
+}
+
+// =====================================================================
+// k_hit_rays_lds — k_hit_rays (rt_hit_rays_walk) through the LDS kernels'
+// walks: the same closest_hit_lds on a caller's rays, over a tree staged as
+// those kernels stage it (the carve is k_camera's, which for !ALL is
+// k_extend_lds's: nodes | leaves (none for SOLO) | sphere records [| moving
+// spheres] | 16-bit lane stacks | fid), with their block size and register
+// budget.  TIME0: k_extend_lds's query — the time-0 tree in LDS, the all-times
+// tree in HBM, time the literal +0.0 (the host refuses other times).
+// Otherwise k_camera<ALL, SOLO>'s query with the ray's own time.  A test
+// probe, not on the render path; it sits here, after the definitions it
+// shares with those kernels, and not next to k_hit_rays.
+// =====================================================================
+template <bool TIME0, bool ALL, bool SOLO>
+__global__ __launch_bounds__(kExtLdsBlock, TIME0 ? RT_EXTLDS_WAVES : RT_CAMERA_WAVES)
+void k_hit_rays_lds(const DevScene sc, const double* __restrict__ rays, const uint32_t n, double* __restrict__ out_t,
+                    int32_t* __restrict__ out_mat, const uint32_t lds_bytes) {
+    static_assert(!(TIME0 && ALL), "k_extend_lds stages the time-0 tree only");
+    extern __shared__ uint4 s_dyn[];
+    if ((ALL ? camera_lds_need(sc) : extend_lds_need(sc)) > lds_bytes || (SOLO && !sc.bvh_solo)) {
+        if (threadIdx.x == 0) raise_fault(RT_FAULT_LDS);     // the carve below would leave the allocation
+        return;
+    }
+    const int nn = ALL ? sc.n_bvh2 : sc.n_fbvh2, nl = ALL ? sc.n_bleaf : (SOLO ? 0 : sc.n_fbleaf);
+    const int ns = ALL ? sc.n_sph : sc.n_fsph, nm = ALL ? sc.n_msph : 0;
+    BvhNode2* s_nodes = reinterpret_cast<BvhNode2*>(s_dyn);
+    BvhLeaf* s_leaves = reinterpret_cast<BvhLeaf*>(s_nodes + nn);
+    SphereRec* s_sph = reinterpret_cast<SphereRec*>(s_leaves + nl);
+    MSphereRec* s_msph = reinterpret_cast<MSphereRec*>(s_sph + ns);
+    uint16_t* s_lstack = reinterpret_cast<uint16_t*>(s_msph + nm);
+    int32_t* s_fid = reinterpret_cast<int32_t*>(s_lstack + (size_t)kExtLdsBlock * (sc.lane_stack > 0 ? sc.lane_stack : 1));
+    stage_lds(s_nodes, ALL ? sc.bvh2 : sc.fbvh2, nn, kExtLdsBlock);
+    if (nl) stage_lds(s_leaves, ALL ? sc.bleaf : sc.fbleaf, nl, kExtLdsBlock);
+    stage_lds(s_sph, ALL ? sc.sph : sc.fsph, ns, kExtLdsBlock);
+    if (ALL) stage_lds(s_msph, sc.msph, nm, kExtLdsBlock);
+    stage_words(reinterpret_cast<uint32_t*>(s_fid), reinterpret_cast<const uint32_t*>(sc.fid), sc.n_fsph, kExtLdsBlock);
+    __syncthreads();
+    const Tree0 t0 = ALL ? tree0_hbm(sc) : Tree0{s_nodes, s_leaves, s_sph, s_fid};
+    const TreeA ta = ALL ? TreeA{s_nodes, s_leaves, s_sph, s_msph} : treeA_hbm(sc);
+    const int LS = sc.lane_stack;
+    for (uint32_t base = ext_first(); base < n; base += gridDim.x * kExtLdsBlock) {
+        const uint32_t k = base + ext_lid();
+        if (k < n) {
+            const double* r = rays + 7 * (size_t)k;
+            const v3 o = mk(r[0], r[1], r[2]);
+            const v3 d = mk(r[3], r[4], r[5]);
+            double t = 0.0;
+            int32_t leaf;
+            if (TIME0) leaf = closest_hit_lds<SOLO>(sc, o, d, 0.0, t, s_lstack + threadIdx.x, LS, t0, ta);
+            else leaf = closest_hit_lds<SOLO, ALL>(sc, o, d, r[6], t, s_lstack + threadIdx.x, LS, t0, ta);
+            out_t[k] = leaf < 0 ? 0.0 : t;
+            out_mat[k] = leaf < 0 ? -1 : sc.leaves[leaf].mat;
+        }
     }
 }
 
@@ -3341,6 +3463,25 @@ hipError_t launch_camera(const DevScene& sc, const RenderParams& rp, const PathS
     if (sc.tree0_any_time) { if (sc.bvh_solo) RT_CAMERA(false, true); else RT_CAMERA(false, false); }
     else { if (sc.bvh_solo) RT_CAMERA(true, true); else RT_CAMERA(true, false); }
 #undef RT_CAMERA
+    return hipGetLastError();
+}
+// the probe's instance for a scene: the one launch_extend_lds (time0) / launch_camera picks of its kernel
+hipError_t launch_hit_rays_lds(const DevScene& sc, bool time0, size_t lds, const double* rays, uint32_t n,
+                               double* out_t, int32_t* out_mat, hipStream_t s) {
+    uint32_t blocks = (n + kExtLdsBlock - 1) / kExtLdsBlock;
+    if (!blocks) return hipSuccess;
+    if (blocks > 1024u) blocks = 1024u;                  // grid-stride, as the persistent kernels
+#define RT_HIT_LDS(T, A, S)                                                                                   \
+    do {                                                                                                      \
+        HIP_RETURN_IF(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hit_rays_lds<T, A, S>),            \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));             \
+        hipLaunchKernelGGL((k_hit_rays_lds<T, A, S>), dim3(blocks), dim3(kExtLdsBlock), lds, s, sc, rays, n,   \
+                           out_t, out_mat, (uint32_t)lds);                                                    \
+    } while (0)
+    if (time0) { if (sc.bvh_solo) RT_HIT_LDS(true, false, true); else RT_HIT_LDS(true, false, false); }
+    else if (sc.tree0_any_time) { if (sc.bvh_solo) RT_HIT_LDS(false, false, true); else RT_HIT_LDS(false, false, false); }
+    else { if (sc.bvh_solo) RT_HIT_LDS(false, true, true); else RT_HIT_LDS(false, true, false); }
+#undef RT_HIT_LDS
     return hipGetLastError();
 }
 constexpr size_t kShadeLeafLds = 32768;      // stage the leaf records when they fit (256 leaves)

@@ -52,6 +52,11 @@ hipError_t launch_curve_depth(const double* cps, const double* eps8, uint32_t n,
 // rt_hit_rays: n rays of 7 doubles (origin, direction, time); the closest hit's t and material
 hipError_t launch_hit_rays(const DevScene& sc, const double* rays, uint32_t n, double* out_t, int32_t* out_mat,
                            hipStream_t s);
+// rt_hit_rays_walk's LDS walks: the same rays through k_extend_lds's query (time0: every ray at time +0.0)
+// or k_camera's, in the instance those kernels' launchers pick for the scene; lds: the scene's
+// extend_lds_bytes (time0) / camera_lds_bytes, not 0
+hipError_t launch_hit_rays_lds(const DevScene& sc, bool time0, size_t lds, const double* rays, uint32_t n,
+                               double* out_t, int32_t* out_mat, hipStream_t s);
 // rt_render_features: passes rp.spp0 .. rp.spp0 + S - 1 of the rp.npix pixels of rp.pixlist, their first-hit
 // features added to feat (RT_FEATURE_DOUBLES running sums per image pixel); only nx, ny, inx, iny, npix,
 // spp0, k0, k1 and pixlist of rp are read

@@ -535,11 +535,32 @@ int render_sel(Scene* s, int nx, int ny, const PixSel& ps, int spp_begin, int sp
 extern "C" {
 
 int rt_hit_rays(int scene, int n, const double* rays, double* out_t, int32_t* out_mat) {
+    return rt_hit_rays_walk(scene, RT_WALK_HBM, n, rays, out_t, out_mat);
+}
+
+int rt_hit_rays_walk(int scene, int walk, int n, const double* rays, double* out_t, int32_t* out_mat) {
     LOCK_SCENE(s, scene);
     if (!s->committed) return fail("scene not committed (rt_scene_commit)");
+    if (walk != RT_WALK_HBM && walk != RT_WALK_LDS_TIME0 && walk != RT_WALK_LDS_CAMERA)
+        return fail("rt_hit_rays_walk: unknown walk " + std::to_string(walk));
     if (n < 0) return fail("ray count must be >= 0");
     if (n > 0 && (!rays || !out_t || !out_mat)) return fail("null pointer");
     if (s->dev.n_med > 0) return fail("rt_hit_rays: the scene has constant media, whose hit test draws random numbers");
+    if (walk == RT_WALK_LDS_TIME0 && s->ext_lds == 0)
+        return fail("rt_hit_rays_walk: this scene's time-0 tree does not run from LDS (rt_scene_info.extend_lds_bytes "
+                    "is 0: no sphere BVH, curves or a Klein set in the world, or a tree over the LDS budget)");
+    if (walk == RT_WALK_LDS_CAMERA && s->cam_lds == 0)
+        return fail("rt_hit_rays_walk: this scene's camera rays do not walk a tree in LDS (rt_scene_info."
+                    "camera_lds_bytes is 0: no sphere BVH, curves or a Klein set in the world, or a tree over the "
+                    "LDS budget)");
+    if (walk == RT_WALK_LDS_TIME0)
+        for (int i = 0; i < n; ++i) {
+            uint64_t bits;
+            std::memcpy(&bits, &rays[7 * (size_t)i + 6], sizeof bits);
+            if (bits != 0)
+                return fail("rt_hit_rays_walk: RT_WALK_LDS_TIME0 takes rays of time +0.0 only (ray " +
+                            std::to_string(i) + " has another time)");
+        }
     CTX_OF(c, s);
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(c->device));
@@ -550,8 +571,13 @@ int rt_hit_rays(int scene, int n, const double* rays, double* out_t, int32_t* ou
     HIPCHK(d_t.ensure((size_t)n * sizeof(double)));
     HIPCHK(d_mat.ensure((size_t)n * sizeof(int32_t)));
     HIPCHK(hipMemcpyAsync(d_rays.p, rays, (size_t)n * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(launch_hit_rays(s->dev, d_rays.as<const double>(), (uint32_t)n, d_t.as<double>(), d_mat.as<int32_t>(),
-                           c->stream));
+    if (walk == RT_WALK_HBM)
+        HIPCHK(launch_hit_rays(s->dev, d_rays.as<const double>(), (uint32_t)n, d_t.as<double>(), d_mat.as<int32_t>(),
+                               c->stream));
+    else
+        HIPCHK(launch_hit_rays_lds(s->dev, walk == RT_WALK_LDS_TIME0, walk == RT_WALK_LDS_TIME0 ? s->ext_lds : s->cam_lds,
+                                   d_rays.as<const double>(), (uint32_t)n, d_t.as<double>(), d_mat.as<int32_t>(),
+                                   c->stream));
     HIPCHK(hipMemcpyAsync(out_t, d_t.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(out_mat, d_mat.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

@@ -445,6 +445,7 @@ int rt_get_scene_info(int scene, rt_scene_info* out) {
     out->commit_upload_ms = s->commit_upload_ms;
     out->commit_sah_ms = s->commit_sah_ms;
     out->commit_threads = s->commit_threads;
+    out->tree0_any_time = d.tree0_any_time;
     return 0;
 }
 

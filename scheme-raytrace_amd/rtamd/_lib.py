@@ -58,7 +58,7 @@ class RtSceneInfo(ctypes.Structure):
                                                "camera_lds_blocks")] + \
                [("cus", ctypes.c_int32), ("curve_stack", ctypes.c_int32), ("commit_ms", ctypes.c_double),
                 ("commit_upload_ms", ctypes.c_double), ("commit_sah_ms", ctypes.c_double),
-                ("commit_threads", ctypes.c_int32), ("reserved0", ctypes.c_int32)]
+                ("commit_threads", ctypes.c_int32), ("tree0_any_time", ctypes.c_int32)]
 
 
 class RtAdaptive(ctypes.Structure):
@@ -93,6 +93,8 @@ _SIGNATURES = {
     "rt_context_get_option": [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)],
     "rt_hit_rays": [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                     ctypes.POINTER(ctypes.c_int32)],
+    "rt_hit_rays_walk": [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                         ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)],
     "rt_scene_begin": [ctypes.c_int, _c_int_p],
     "rt_scene_destroy": [ctypes.c_int],
     "rt_add_texture_constant": [ctypes.c_int, _c_double_p, _c_int_p],

@@ -265,15 +265,20 @@ def render_shard_device(scene, nx, ny, spp_begin, spp_count, seed, shard, nshard
     return h
 
 
-def hit_rays(scene, rays, ctx=None):
-    """rt_hit_rays: rays = (n, 7) float64 (origin, direction, time); returns
-    (t, material id) arrays, material -1 for a miss."""
+#: rt_hit_rays_walk's walks (include/rt.h)
+WALK_HBM, WALK_LDS_TIME0, WALK_LDS_CAMERA = 0, 1, 2
+
+
+def hit_rays(scene, rays, ctx=None, walk=WALK_HBM):
+    """rt_hit_rays_walk: rays = (n, 7) float64 (origin, direction, time); returns
+    (t, material id) arrays, material -1 for a miss.  ``walk``: the closest-hit
+    walk the rays take (WALK_HBM is rt_hit_rays)."""
     h = upload(scene, ctx)
     r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 7)
     n = r.shape[0]
     t = np.zeros(n)
     m = np.zeros(n, dtype=np.int32)
-    call("rt_hit_rays", h, n, r.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+    call("rt_hit_rays_walk", h, int(walk), n, r.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
          t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), m.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
     return t, m
 

@@ -13,6 +13,9 @@ import numpy as np
 import pytest
 
 from conftest import host_threads
+from hit_ray_cases import many_spheres_scene as _many_spheres_scene
+from hit_ray_cases import moving_mix_scene as _moving_mix_scene
+from hit_ray_cases import static_cover_scene as _static_cover_scene
 from rtamd import gpu, scenes
 from rtamd._lib import RtError
 
@@ -250,57 +253,8 @@ def test_sah_builders_same_image_bitwise(sched, monkeypatch, wavefront):
     assert np.array_equal(imgs[0], imgs[1])
 
 
-def _moving_mix_scene(nx, ny):
-    """Moving spheres whose shutters do not start at 0 (center(0) is an
-    extrapolation), a degenerate shutter (t0 = t1: center(0) is NaN, never
-    hit), static spheres, all three materials, and a camera shutter [0, 1]."""
-    from rtamd import scene as g, vec as v
-    from rtamd.rng import HostStream
-    rr = HostStream(0x5EED0101)
-    mats = [g.make_lambertian(g.constant_texture(v.vec3(0.5, 0.6, 0.7))),
-            g.make_metal(g.constant_texture(v.vec3(0.8, 0.7, 0.6)), 0.3), g.make_dielectric(1.5)]
-    objs = [g.make_sphere(v.vec3(0, -1000, 0), 1000, mats[0])]
-    for i in range(60):
-        c0 = v.vec3(rr() * 8 - 4, 0.2 + rr() * 0.5, rr() * 8 - 4)
-        c1 = v.sum(c0, v.vec3(rr() - 0.5, rr(), rr() - 0.5))
-        m = mats[i % 3]
-        if i % 4 == 0:
-            objs.append(g.make_sphere(c0, 0.25, m))
-        elif i % 4 == 1:
-            objs.append(g.make_moving_sphere(c0, c1, 0.5, 1.5, 0.2, m))
-        elif i % 4 == 2:
-            objs.append(g.make_moving_sphere(c0, c1, -1.0, 0.25, 0.3, m))
-        else:
-            objs.append(g.make_moving_sphere(c0, c1, 0.0, 1.0, 0.2, m))
-    objs.append(g.make_moving_sphere(v.vec3(0, 1, 0), v.vec3(0, 2, 0), 0.5, 0.5, 0.5, mats[0]))
-    return g.make_scene(objs, scenes.camera_for(nx, ny), g.sky_color)
-
-
-def _static_cover_scene(nx, ny):
-    """The cover scene with every moving sphere frozen where it starts: no
-    moving spheres, so the time-0 tree serves camera rays too (k_camera<false>)."""
-    from rtamd import scene as g
-    sc = scenes.random_scene(nx, ny)
-    objs = [g.make_sphere(o.args[0], o.args[4], o.args[5]) if o.kind == "moving_sphere" else o
-            for o in sc.obj_list]
-    return g.make_scene(objs, sc.camera, sc.sky_function)
-
-
-def _many_spheres_scene(nx, ny):
-    """2000 small spheres of all three materials: the trees outgrow the LDS
-    kernels' budget, so every launch takes the HBM-tree kernels."""
-    from rtamd import scene as g, vec as v
-    from rtamd.rng import HostStream
-    rr = HostStream(0x5EED0102)
-    mats = [g.make_lambertian(g.constant_texture(v.vec3(0.6, 0.5, 0.4))),
-            g.make_metal(g.constant_texture(v.vec3(0.8, 0.8, 0.7)), 0.2), g.make_dielectric(1.5)]
-    objs = [g.make_sphere(v.vec3(0, -1000, 0), 1000, mats[0])]
-    for i in range(2000):
-        objs.append(g.make_sphere(v.vec3(rr() * 20 - 10, rr() * 2, rr() * 20 - 10), 0.05 + 0.1 * rr(), mats[i % 3]))
-    return g.make_scene(objs, scenes.camera_for(nx, ny), g.sky_color)
-
-
-@pytest.mark.parametrize("make", [_static_cover_scene, _many_spheres_scene])
+@pytest.mark.parametrize("make", [_static_cover_scene, _many_spheres_scene],
+                         ids=["_static_cover_scene", "_many_spheres_scene"])
 def test_kernel_paths_match_flat_list_bitwise(sched, monkeypatch, make):
     """Scenes that take the other closest-hit paths (time-0 tree for camera
     rays; trees too big for LDS) equal the brute-force flat list bit for bit."""
@@ -316,7 +270,8 @@ def test_kernel_paths_match_flat_list_bitwise(sched, monkeypatch, make):
     assert np.array_equal(imgs[0], imgs[1])
 
 
-@pytest.mark.parametrize("make", [scenes.random_scene, _moving_mix_scene])
+@pytest.mark.parametrize("make", [scenes.random_scene, _moving_mix_scene],
+                         ids=["random_scene", "_moving_mix_scene"])
 def test_time0_bvh_matches_all_times_bvh_bitwise(sched, monkeypatch, make):
     """Scattered rays (time 0) traverse the time-0 tree with moving spheres
     frozen at center(0); the image equals the one from the all-times tree and
