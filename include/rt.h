@@ -511,6 +511,43 @@ int rt_denoise(int ctx, int nx, int ny, const struct rt_denoise* p,
                const double* accum, const double* accum2 /*nullable*/, const uint32_t* count /*nullable*/, uint32_t sample_count,
                const double* feat, uint32_t feat_count, double* out_mean);
 
+/* ---- image textures — t:image-texture, texture.scm:36-50 ------------------------------------------------
+ * Opt-in: nothing above changes.  RT_ABI_VERSION stays 7; test RT_HAS_IMAGE_TEXTURE for this entry point.
+ *
+ * rgb holds nx*ny texels of 3 BYTES (r, g, b), row 0 first, and row 0 is the TOP of the image (v = 1).  The
+ * reference's `data` vector may hold any numbers (it takes floor->exact of each); this ABI takes bytes.  The
+ * bytes are copied at the call.  The texture id is used like any other: as a material's albedo / emission, as
+ * a checker's child (a checker hands u, v, p on to its children), as a constant medium's phase texture.
+ *
+ * The lookup for a hit with (u, v), all f64, in this operation order (repair R4, DESIGN.md §2: as written the
+ * reference indexes `data` with an inexact number, which vector-ref refuses; the indices are floored):
+ *   i = u * nx;  j = (1 - v) * ny - 0.001
+ *   if (!(i >= 0)) i = 0;  if (!(j >= 0)) j = 0            (so a NaN lands on 0; no NaN is ever cast)
+ *   if (i > nx - 1) i = nx - 1;  if (j > ny - 1) j = ny - 1
+ *   ii = (int)floor(i);  jj = (int)floor(j);  texel = ii + nx * jj
+ *   colour channel = (double)byte / 255.0, a correctly rounded f64 division (Gauche's exact (/ k 255) stored
+ *   in an f64vector)
+ * rtamd.image.lookup is the NumPy restatement.
+ *
+ * The hit record's u, v:
+ *   rects (box faces are rects): geometry.scm:388-389, 407-408, 426-427 — with (a, b) the hit point's
+ *     in-plane coordinates on the instance-local ray (XY: x, y; XZ: x, z; YZ: y, z),
+ *     u = (a - a0) / (a1 - a0), v = (b - b0) / (b1 - b0);
+ *   flip-normals, translate and rotate-y pass u, v through; constant media, Klein sets and curves give 0, 0;
+ *   spheres and moving spheres (repair R5: get-sphere-uv, geometry.scm:138-144, takes (atan z z) and the asin of
+ *     an unnormalised y, which is complex for |y| > 1 and makes the comparison raise) — the book's formula on
+ *     the unit normal n = (p - centre(time)) * (1 / radius), before any flip:
+ *     phi = atan2(n.z, n.x);  theta = asin(n.y < -1 ? -1 : n.y > 1 ? 1 : n.y)
+ *     u = 1 - (phi + pi) / (2 * pi);  v = (theta + pi / 2) / pi       (divisions, not reciprocal products)
+ *     atan2 / asin are the device library's (within an ulp or two of the C library's).
+ * Image textures do not switch the exact libm on (RT_OPT_EXACT_LIBM): nothing in a lookup is a sin or cos.
+ *
+ * Refused with an rt_last_error message and before any device work: a null rgb or out_tex, nx or ny < 1,
+ * nx*ny > 2^26, a scene whose images together would exceed 2^31 - 1 texels, a bad scene handle, a committed
+ * scene.  Storage: 4 bytes per texel in device memory (RGBX, one load per lookup), freed with the scene. */
+#define RT_HAS_IMAGE_TEXTURE 1
+int rt_add_texture_image(int scene, const uint8_t* rgb /* nx*ny*3, row 0 = top */, int nx, int ny, int* out_tex);
+
 #ifdef __cplusplus
 }
 #endif

@@ -776,6 +776,11 @@ int commit_scene(Scene* s, int world) {
     d.has_perlin = s->have_perlin ? 1 : 0;
     d.has_noise_tex = 0;
     for (const auto& t : s->texs) if (t.type == TEX_NOISE || t.type == TEX_MARBLE) d.has_noise_tex = 1;
+    d.has_image_tex = 0;
+    for (const auto& t : s->texs) if (t.type == TEX_IMAGE) d.has_image_tex = 1;
+    if (d.has_image_tex) {
+        if (int rc = upload(s->d_teximg, s->teximg, &d.teximg)) return rc;
+    }
     if (s->have_perlin) {
         if (int rc = upload(s->d_ranvec, s->ranvec, &d.ranvec)) return rc;
         if (int rc = upload(s->d_perm, s->perm, &d.perm)) return rc;

@@ -22,7 +22,7 @@ constexpr double kPi = 3.141592653589793;      // math.const pi
 constexpr int kMaxChain = 4;                   // instance ops per leaf chain
 // device fault bits: RT_FAULT_* (include/rt.h); rt_kernels.hip g_fault, reported by render_impl
 
-enum TexType : int32_t { TEX_CONSTANT = 0, TEX_CHECKER = 1, TEX_NOISE = 2, TEX_MARBLE = 3 };
+enum TexType : int32_t { TEX_CONSTANT = 0, TEX_CHECKER = 1, TEX_NOISE = 2, TEX_MARBLE = 3, TEX_IMAGE = 4 };
 enum MatType : int32_t { MAT_LAMBERTIAN = 0, MAT_METAL = 1, MAT_DIELECTRIC = 2, MAT_DIFFUSE_LIGHT = 3 };
 enum LeafType : int32_t { LEAF_SPHERE = 0, LEAF_MSPHERE = 1, LEAF_RECT_XY = 2, LEAF_RECT_XZ = 3,
                           LEAF_RECT_YZ = 4, LEAF_BEZIER = 5, LEAF_MEDIUM = 6, LEAF_KLEIN = 7 };
@@ -32,9 +32,9 @@ constexpr int32_t GROUP_BVH = 8;               // group type: BVH over world-lev
 constexpr int kFeatCurves = 1, kFeatExtra = 2;
 enum ChainOp : int32_t { OP_TRANSLATE = 0, OP_ROTATE_Y = 1 };
 
-struct DevTexture {            // texture.scm:12-34
-    int32_t type, a, b, pad;   // checker: a = even, b = odd
-    double r, g, bl, scale;
+struct DevTexture {            // texture.scm:12-50
+    int32_t type, a, b, off;   // checker: a = even, b = odd; image: a = nx, b = ny, off = its first texel in
+    double r, g, bl, scale;    // DevScene::teximg (row 0 = top, nx texels per row)
 };
 struct DevMaterial {           // material.scm:24-111
     int32_t type, tex;
@@ -199,6 +199,10 @@ struct DevScene {
     // the world's leaf ids in list order (hit-obj-list's order; 0 entries in scenes with media): what a ray
     // that lies in a rect's plane is scanned in (list_closest)
     const int32_t* order;  int32_t n_order;
+    // image textures (t:image-texture, texture.scm:36-50): every image's texels in one buffer, one dword per
+    // texel (R | G << 8 | B << 16), so a lookup is one load; has_image_tex selects the kernels' kTexImage instances
+    int32_t has_image_tex;                     // some texture is an image
+    const uint32_t* teximg;
 };
 
 // Wavefront path state, SoA, one slot per live path (ping-pong buffers).

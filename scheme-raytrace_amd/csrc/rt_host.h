@@ -149,6 +149,7 @@ struct Context {
 struct Scene {
     int ctx = -1;
     std::vector<DevTexture> texs;
+    std::vector<uint32_t> teximg;     // the image textures' texels (rt_add_texture_image), as DevScene::teximg
     std::vector<DevMaterial> mats;
     std::vector<Obj> objs;
     double cam[RT_CAMERA_DOUBLES] = {0};
@@ -168,6 +169,7 @@ struct Scene {
     DevBuf d_dev;                                  // a device copy of `dev` (kernels that take the scene by pointer)
     DevBuf d_leaf_cls;
     DevBuf d_order;
+    DevBuf d_teximg;                               // the image textures' texels
     size_t ext_lds = 0;                            // k_extend_lds: LDS bytes (0 = not used) and grid cap
     uint32_t ext_lds_blocks = 0;
     size_t cam_lds = 0;                            // k_camera (fused raygen + depth-0 extend), same

@@ -17,7 +17,7 @@
 //   k_finish<F> the depth tail: extend+shade looped  (same code; persistent lanes refill
 //               per lane for the last paths           from the remaining path list)
 //
-//   k_features<F,PN> first-hit feature buffers       (an extension, include/rt.h: camera ray +
+//   k_features<F,TL> first-hit feature buffers       (an extension, include/rt.h: camera ray +
 //               (albedo, normal, t, hits) of the      closest hit + hit record + texture, no bounce)
 //               camera samples a render takes
 //
@@ -2728,9 +2728,56 @@ __device__ __forceinline__ bool checker_odd(const v3 p) {
     return sines < 0.0;
 }
 
-// PN = false compiles the noise / marble cases out (scenes without them)
-template <bool PN>
-__device__ __forceinline__ v3 tex_value(const DevScene& sc, const PerlinLds& P, int id, v3 p) {   // texture.scm
+// The hit record's u, v (image textures only; compiled into the kTexImage instances).  Rects: geometry.scm:388-389,
+// 407-408, 426-427 on the in-plane coordinates of the point on the instance-local ray.  Spheres (repair R5,
+// DESIGN.md §2): the book's formula on the unit normal n = (p - centre(time)) * inv_r, not flipped.
+// Media, Klein sets and curves: 0 0.
+// sphere_uv is a call, not inlined: the device library's f64 atan2 and asin inlined cost every image instance
+// 60-70 VGPRs (lambertian k_shade 231 instead of 167: 2 waves per SIMD instead of 3) whether or not a hit is on
+// a sphere; out of line they cost 32 B of scratch per lane for the call.  cornell_image 1024x1024x256: 204.0 ms
+// against 216.8 inlined (profiles/image_texture/feature_cost.txt)
+__device__ __noinline__ void sphere_uv(const v3 n, double& u, double& v) {
+    const double phi = atan2(n.z, n.x);
+    const double ny = n.y < -1.0 ? -1.0 : (n.y > 1.0 ? 1.0 : n.y);
+    const double theta = asin(ny);
+    u = 1.0 - (phi + kPi) / (2.0 * kPi);
+    v = (theta + kPi / 2.0) / kPi;
+}
+__device__ __forceinline__ void hit_uv(const DevScene& sc, const LeafInfo& li, const v3 pt, const v3 n, double& u, double& v) {
+    u = 0.0; v = 0.0;
+    if (li.type == LEAF_SPHERE || li.type == LEAF_MSPHERE) {
+        sphere_uv(n, u, v);
+    } else if (li.type == LEAF_RECT_XY || li.type == LEAF_RECT_XZ || li.type == LEAF_RECT_YZ) {
+        const RectRec R = sc.rect[li.local];
+        const double a = (li.type == LEAF_RECT_YZ) ? pt.y : pt.x;       // XY: (x, y); XZ: (x, z); YZ: (y, z)
+        const double b = (li.type == LEAF_RECT_XY) ? pt.y : pt.z;
+        u = (a - R.a0) / (R.a1 - R.a0);
+        v = (b - R.b0) / (R.b1 - R.b0);
+    }
+}
+// t:image-texture's lookup (texture.scm:36-50 with repair R4, include/rt.h "image textures"): indices clamped
+// as the reference clamps them, then floored; a NaN lands on 0 and is never cast.  One dword per texel (RGBX).
+__device__ __forceinline__ v3 image_texel(const DevScene& sc, const DevTexture& t, const double u, const double v) {
+    const int nx = t.a, ny = t.b;
+    double i = u * (double)nx;
+    double j = (1.0 - v) * (double)ny - 0.001;
+    if (!(i >= 0.0)) i = 0.0;
+    if (!(j >= 0.0)) j = 0.0;
+    if (i > (double)(nx - 1)) i = (double)(nx - 1);
+    if (j > (double)(ny - 1)) j = (double)(ny - 1);
+    const int ii = (int)floor(i), jj = (int)floor(j);
+    const uint32_t px = sc.teximg[(size_t)(uint32_t)t.off + (size_t)ii + (size_t)nx * (size_t)jj];
+    return mk((double)(px & 255u) / 255.0, (double)((px >> 8) & 255u) / 255.0, (double)((px >> 16) & 255u) / 255.0);
+}
+
+// TL: the texture level a kernel is compiled for.  kTexPlain compiles the noise / marble cases out (scenes
+// without them); kTexImage adds image textures (and the hit record's u, v) to kTexPerlin
+constexpr int kTexPlain = 0, kTexPerlin = 1, kTexImage = 2;
+static int scene_tex_level(const DevScene& sc) {     // the instances a scene's launches take
+    return sc.has_image_tex ? kTexImage : sc.has_noise_tex ? kTexPerlin : kTexPlain;
+}
+template <int TL>
+__device__ __forceinline__ v3 tex_value(const DevScene& sc, const PerlinLds& P, int id, v3 p, const double u, const double v) {   // texture.scm
     for (int guard = 0; guard < 64; ++guard) {
         const DevTexture t = sc.texs[id];
         if (t.type == TEX_CONSTANT) return mk(t.r, t.g, t.bl);
@@ -2738,7 +2785,10 @@ __device__ __forceinline__ v3 tex_value(const DevScene& sc, const PerlinLds& P, 
             id = checker_odd(p) ? t.b : t.a;
             continue;
         }
-        if (!PN) return mk(0.0, 0.0, 0.0);
+        if constexpr (TL >= kTexImage) {
+            if (t.type == TEX_IMAGE) return image_texel(sc, t, u, v);   // :36-50
+        }
+        if (TL < kTexPerlin) return mk(0.0, 0.0, 0.0);
         if (t.type == TEX_NOISE) {                                   // :25-28
             const double nz = perlin_noise(P, p * t.scale);
             return mk(1.0, 1.0, 1.0) * nz;
@@ -2768,12 +2818,13 @@ __device__ __forceinline__ double pow5(const double x) {
 }
 // a hit's texture value from its leaf record: constant and checker-of-constants
 // colours are inline (texture.scm:12-23); anything else goes through tex_value
-template <bool PN>
-__device__ __forceinline__ v3 leaf_tex(const DevScene& sc, const PerlinLds& P, const LeafInfo& li, const v3 p) {
+template <int TL>
+__device__ __forceinline__ v3 leaf_tex(const DevScene& sc, const PerlinLds& P, const LeafInfo& li, const v3 p,
+                                       const double u, const double v) {
     if (li.tex_kind == TK_CONSTANT) return mk(li.albedo[0], li.albedo[1], li.albedo[2]);
     if (li.tex_kind == TK_CHECKER_CONST)
         return checker_odd(p) ? mk(li.albedo2[0], li.albedo2[1], li.albedo2[2]) : mk(li.albedo[0], li.albedo[1], li.albedo[2]);
-    return tex_value<PN>(sc, P, li.tex, p);
+    return tex_value<TL>(sc, P, li.tex, p, u, v);
 }
 __device__ __forceinline__ v3 reflect(v3 v, v3 n) { return v - n * (2.0 * dot(v, n)); }  // material.scm:41-43
 
@@ -2845,11 +2896,12 @@ __device__ __forceinline__ v3 light_random(const DevLight& L, const v3 o, Rng& g
 // queue holds (compile-time; -1 = any, used by the tail kernel).  Returns true
 // if the path continues (p holds the scattered ray, new throughput, depth+1);
 // otherwise L is the terminal radiance (emission or 0).
+// TL: the texture level (tex_value).
 // LS = false compiles the light-sampling mixture (f2) out: scenes without a
 // light target never take it, and its constants cost scalar registers.
 // leaves: the leaf records (LDS in k_shade when the table is small, else HBM)
 // trig: rt_libm.h's sin / cos table for the lambertian bounce (an LDS copy in k_shade)
-template <int MATF, bool PN = true, bool LS = true, bool EX = true>
+template <int MATF, int TL = kTexPerlin, bool LS = true, bool EX = true>
 __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P, const RenderParams& rp,
                                           PathRegs& p, const double t, const int32_t leaf, v3& L,
                                           const LeafInfo* __restrict__ leaves,
@@ -2883,13 +2935,17 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
     } else {
         nrm = d * -1.0;                                      // curve: (v:scale (dir r) -1), bezier.scm:204
     }
+    double tu = 0.0, tv = 0.0;                               // the record's u, v: read by image textures only
+    if constexpr (TL >= kTexImage) {
+        if (li.tex_kind == TK_GENERIC) hit_uv(sc, li, pt, nrm, tu, tv);
+    }
     if (li.flip) nrm = nrm * -1.0;                          // flip-normals :438
     if (li.chain >= 0) chain_hit(sc.chains[li.chain], pt, nrm);
     const int mt = (MATF >= 0) ? MATF : li.mtype;
     const v3 rdir = p.d;
     const bool can_continue = p.depth < (uint32_t)kMaxDepth;
     if (mt == MAT_DIFFUSE_LIGHT) {                           // material.scm:103-111
-        if (dot(nrm, rdir) < 0.0) L = leaf_tex<PN>(sc, P, li, pt);
+        if (dot(nrm, rdir) < 0.0) L = leaf_tex<TL>(sc, P, li, pt, tu, tv);
         return false;
     }
     if (!can_continue) return false;                         // depth cap (main.scm:112,119)
@@ -2926,7 +2982,7 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
         if (cosine < 0.0) cosine = 0.0;
         const double spdf = div_ia(cosine, kPi, kInvPi);
         const double ipdf = 1.0 / pdf_val;
-        const v3 att = leaf_tex<PN>(sc, P, li, pt);
+        const v3 att = leaf_tex<TL>(sc, P, li, pt, tu, tv);
         p.T = mk((p.T.x * (att.x * spdf)) * ipdf, (p.T.y * (att.y * spdf)) * ipdf,
                  (p.T.z * (att.z * spdf)) * ipdf);
         p.d = dir;
@@ -2956,7 +3012,7 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
         if (cosine < 0.0) cosine = 0.0;
         const double spdf = div_ia(cosine, kPi, kInvPi);     // scattering-pdf
         const double ipdf = 1.0 / pdf;
-        const v3 att = leaf_tex<PN>(sc, P, li, pt);
+        const v3 att = leaf_tex<TL>(sc, P, li, pt, tu, tv);
         // forward form of  e + ((att*spdf) (*) L_next) * (1/pdf)  (main.scm:113-118)
         p.T = mk((p.T.x * (att.x * spdf)) * ipdf, (p.T.y * (att.y * spdf)) * ipdf,
                  (p.T.z * (att.z * spdf)) * ipdf);
@@ -2972,7 +3028,7 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
         }
         const v3 sd = reflected + s * li.mparam;
         if (!(dot(sd, nrm) > 0.0)) return false;             // absorbed: emitted 0
-        const v3 att = leaf_tex<PN>(sc, P, li, pt);
+        const v3 att = leaf_tex<TL>(sc, P, li, pt, tu, tv);
         p.T = p.T * att;
         p.d = sd;
     } else {                                                 // dielectric material.scm:76-101 (R2)
@@ -3003,17 +3059,17 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
     return true;
 }
 
-// the fused curve extend's shading (k_extend_curves<FUSE>): any material, no Perlin tables (PN false: the
-// table reference is never read), no light mixture
+// the fused curve extend's shading (k_extend_curves<FUSE>): any material, no Perlin tables (kTexPlain: the
+// table reference is never read), no image textures, no light mixture
 template <bool EX>
 __device__ __forceinline__ bool fused_shade(const DevScene& sc, const RenderParams& rp, PathRegs& p, const double t,
                                             const int32_t leaf, v3& L) {
-    return shade_hit<-1, false, false, EX>(sc, *reinterpret_cast<const PerlinLds*>(sc.leaves), rp, p, t, leaf, L, sc.leaves);
+    return shade_hit<-1, kTexPlain, false, EX>(sc, *reinterpret_cast<const PerlinLds*>(sc.leaves), rp, p, t, leaf, L, sc.leaves);
 }
 
-template <bool PN = true>
+template <int TL = kTexPerlin>
 __device__ __forceinline__ void stage_perlin(const DevScene& sc, PerlinLds& P) {
-    if (PN && sc.has_perlin) {   // the Perlin tables (perlin.scm:32-36 data) into LDS
+    if (TL >= kTexPerlin && sc.has_perlin) {   // the Perlin tables (perlin.scm:32-36 data) into LDS
         for (int k = threadIdx.x; k < 768; k += blockDim.x) { P.ranvec[k] = sc.ranvec[k]; P.perm[k] = sc.perm[k]; }
         __syncthreads();
     }
@@ -3034,13 +3090,13 @@ __device__ __forceinline__ void stage_perlin(const DevScene& sc, PerlinLds& P) {
 #endif
 // the exact libm's lambertian kernels without Perlin tables or the light mixture (EX) at 4 waves: with the
 // bounce angles' in-range sin / cos (rt_cos_sin) they need 137 VGPRs left alone and fit 128 with no spill
-template <int MAT, bool PN, bool LS, bool EX>
+template <int MAT, int TL, bool LS, bool EX>
 constexpr int shade_waves() {
     return (MAT == MAT_METAL || MAT == MAT_DIELECTRIC) ? RT_SHADE_WAVES_MD
-         : (MAT == MAT_LAMBERTIAN && EX && !PN && !LS) ? 4 : RT_SHADE_WAVES;
+         : (MAT == MAT_LAMBERTIAN && EX && TL == kTexPlain && !LS) ? 4 : RT_SHADE_WAVES;
 }
-template <int MAT, bool PN, bool LS, bool LL, bool EX>
-__global__ __launch_bounds__(256, (shade_waves<MAT, PN, LS, EX>())) void k_shade(const DevScene* __restrict__ scp, const RenderParams rp,
+template <int MAT, int TL, bool LS, bool LL, bool EX>
+__global__ __launch_bounds__(256, (shade_waves<MAT, TL, LS, EX>())) void k_shade(const DevScene* __restrict__ scp, const RenderParams rp,
                                                                 const PathState in, const HitRec* __restrict__ hq,
                                                                 const QView qv, PathState out,
                                                                 uint32_t* __restrict__ out_counts, uint32_t shard_cap,
@@ -3052,14 +3108,14 @@ __global__ __launch_bounds__(256, (shade_waves<MAT, PN, LS, EX>())) void k_shade
     __shared__ double s_trig[kTrig ? 4 * 112 : 2];
     if (kTrig)
         for (int k = threadIdx.x; k < 4 * 112; k += 256) s_trig[k] = rtlibm::kSinCosTab[k];
-    // dynamic LDS: the leaf records (LL), then the Perlin tables (PN) — only
+    // dynamic LDS: the leaf records (LL), then the Perlin tables (TL >= kTexPerlin) — only
     // what the scene uses, so the block's LDS does not cap the occupancy
     extern __shared__ uint4 s_leafdyn[];
     LeafInfo* s_leaves = reinterpret_cast<LeafInfo*>(s_leafdyn);
     PerlinLds& P = *reinterpret_cast<PerlinLds*>(s_leafdyn + (LL ? (size_t)sc.n_leaves * sizeof(LeafInfo) / 16 : 0));
     if (LL) stage_lds(s_leaves, sc.leaves, sc.n_leaves, 256);
-    stage_perlin<PN>(sc, P);                         // (its barrier also covers the leaf and table staging)
-    if ((LL || kTrig) && !(PN && sc.has_perlin)) __syncthreads();
+    stage_perlin<TL>(sc, P);                         // (its barrier also covers the leaf and table staging)
+    if ((LL || kTrig) && !(TL >= kTexPerlin && sc.has_perlin)) __syncthreads();
     const LeafInfo* leaves = LL ? s_leaves : sc.leaves;
     const QMap qm = qmap(qv);
     uint32_t n = 0;
@@ -3074,7 +3130,7 @@ __global__ __launch_bounds__(256, (shade_waves<MAT, PN, LS, EX>())) void k_shade
             const HitRec H = hq[qphys(qm, k)];
             load_path(in, H.slot, p, rp, depth);
             v3 L;
-            alive = shade_hit<MAT, PN, LS, EX>(sc, P, rp, p, H.t, H.leaf, L, leaves, kTrig ? s_trig : rtlibm::kSinCosTab);
+            alive = shade_hit<MAT, TL, LS, EX>(sc, P, rp, p, H.t, H.leaf, L, leaves, kTrig ? s_trig : rtlibm::kSinCosTab);
             if (!alive) write_sample(rp, p, L);
         }
         const uint32_t slot = block_append<1>(alive ? 0 : -1, out_counts, shard_cap, s_cnt);
@@ -3090,10 +3146,10 @@ __global__ __launch_bounds__(256, (shade_waves<MAT, PN, LS, EX>())) void k_shade
 #ifndef RT_FINISH_WAVES
 #define RT_FINISH_WAVES 4             // plain-sphere tails without Perlin / light mixture: 128 VGPRs, 4 waves per SIMD
 #endif                                // (the compiler's choice is 143: 3 waves; the other variants would spill at 128)
-template <int F, bool PN, bool LSM>
-constexpr int finish_waves() { return (F == 0 && !PN && !LSM) ? RT_FINISH_WAVES : 1; }
-template <int F, bool PN, bool LSM, bool SOLO = false, bool EX = false>
-__global__ __launch_bounds__(256, (finish_waves<F, PN, LSM>())) void k_finish(const DevScene* __restrict__ scp, const RenderParams rp, const PathState st,
+template <int F, int TL, bool LSM>
+constexpr int finish_waves() { return (F == 0 && TL == kTexPlain && !LSM) ? RT_FINISH_WAVES : 1; }
+template <int F, int TL, bool LSM, bool SOLO = false, bool EX = false>
+__global__ __launch_bounds__(256, (finish_waves<F, TL, LSM>())) void k_finish(const DevScene* __restrict__ scp, const RenderParams rp, const PathState st,
                                                 const QView in, uint32_t n,
                                                 unsigned long long* __restrict__ tail_ctl, int tree0_lds,
                                                 const uint32_t depth) {
@@ -3130,7 +3186,7 @@ __global__ __launch_bounds__(256, (finish_waves<F, PN, LSM>())) void k_finish(co
         t0 = Tree0{s_nodes, s_leaves, s_sph, sc.fid};
         __syncthreads();
     }
-    stage_perlin<PN>(sc, P);
+    stage_perlin<TL>(sc, P);
     // Persistent lanes: a lane whose path ended takes the next unstarted one
     // (one atomic per wave per refill), so a wave is not held by its longest
     // path while its other lanes idle.  tail_ctl[0] counts segments,
@@ -3175,7 +3231,7 @@ __global__ __launch_bounds__(256, (finish_waves<F, PN, LSM>())) void k_finish(co
             v3 L;
             bool cont = false;
             if (leaf < 0) L = sky_radiance(sc, p.d);
-            else cont = shade_hit<-1, PN, LSM, EX>(sc, P, rp, p, t, leaf, L, sc.leaves);
+            else cont = shade_hit<-1, TL, LSM, EX>(sc, P, rp, p, t, leaf, L, sc.leaves);
             if (!cont) { write_sample(rp, p, L); active = false; }
         }
     }
@@ -3185,7 +3241,7 @@ __global__ __launch_bounds__(256, (finish_waves<F, PN, LSM>())) void k_finish(co
 }
 
 // =====================================================================
-// k_features<F, PN> — first-hit feature buffers (include/rt.h, "feature buffers"; an extension, no
+// k_features<F, TL> — first-hit feature buffers (include/rt.h, "feature buffers"; an extension, no
 // counterpart in the reference).  One lane per listed pixel, in the list's (16x16-tile) order; the lane
 // loops over the call's passes and keeps its eight running sums in registers, so sample order is fixed
 // without atomics, and writes one 64-byte record.  Every pass takes the camera ray the render traces for
@@ -3195,8 +3251,9 @@ __global__ __launch_bounds__(256, (finish_waves<F, PN, LSM>())) void k_finish(co
 // The hit record as shade_hit forms it before the material's scatter: the point on the (instance-local)
 // ray and the normal, flipped and taken back out of the instance chain, not renormalised.  Restated here:
 // shade_hit's own copy is scheduled into every shade kernel's register budget.
+template <int TL>
 __device__ __forceinline__ void feature_hit(const DevScene& sc, const LeafInfo& li, const v3 o0, const v3 d0,
-                                            const double time, const double t, v3& pt, v3& nrm) {
+                                            const double time, const double t, v3& pt, v3& nrm, double& tu, double& tv) {
     v3 o = o0, d = d0;
     if (li.chain >= 0) chain_ray(sc.chains[li.chain], o, d);
     pt = o + d * t;
@@ -3223,19 +3280,23 @@ __device__ __forceinline__ void feature_hit(const DevScene& sc, const LeafInfo& 
     } else {
         nrm = d * -1.0;
     }
+    tu = 0.0; tv = 0.0;
+    if constexpr (TL >= kTexImage) {
+        if (li.tex_kind == TK_GENERIC) hit_uv(sc, li, pt, nrm, tu, tv);
+    }
     if (li.flip) nrm = nrm * -1.0;
     if (li.chain >= 0) chain_hit(sc.chains[li.chain], pt, nrm);
 }
-template <int F, bool PN>
+template <int F, int TL>
 __global__ __launch_bounds__(256) void k_features(const DevScene sc, const RenderParams rp, const uint32_t S,
                                                   double* __restrict__ feat) {
-    // dynamic LDS: the per-lane BVH stack (256 x sc.lane_stack words), then the Perlin tables (PN)
+    // dynamic LDS: the per-lane BVH stack (256 x sc.lane_stack words), then the Perlin tables (TL >= kTexPerlin)
     extern __shared__ uint32_t s_lstack[];
     constexpr bool BEZ = (F & kFeatCurves) != 0;
     __shared__ BezWave s_bw[BEZ ? 4 : 1];
     const int LS = sc.lane_stack;
     PerlinLds& P = *reinterpret_cast<PerlinLds*>(s_lstack + (size_t)256 * (size_t)(LS > 0 ? LS : 1));
-    stage_perlin<PN>(sc, P);
+    stage_perlin<TL>(sc, P);
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;
     if (q >= rp.npix) return;
     double* rec = feat + (size_t)RT_FEATURE_DOUBLES * rp.pixlist[q];
@@ -3256,8 +3317,9 @@ __global__ __launch_bounds__(256) void k_features(const DevScene sc, const Rende
         } else {
             const LeafInfo& li = sc.leaves[leaf];
             v3 pt;
-            feature_hit(sc, li, o, d, time, t, pt, n);
-            a = li.mtype == MAT_DIELECTRIC ? mk(1.0, 1.0, 1.0) : leaf_tex<PN>(sc, P, li, pt);
+            double tu, tv;
+            feature_hit<TL>(sc, li, o, d, time, t, pt, n, tu, tv);
+            a = li.mtype == MAT_DIELECTRIC ? mk(1.0, 1.0, 1.0) : leaf_tex<TL>(sc, P, li, pt, tu, tv);
             tt = t;
             hit = 1.0;
         }
@@ -3376,13 +3438,14 @@ hipError_t launch_hit_rays(const DevScene& sc, const double* rays, uint32_t n, d
 hipError_t launch_features(const DevScene& sc, const RenderParams& rp, uint32_t S, double* feat, hipStream_t s) {
     const uint32_t blocks = (rp.npix + 255u) / 256u;
     if (!blocks || !S) return hipSuccess;
-    const bool pn = sc.has_noise_tex != 0;
+    const int tl = scene_tex_level(sc);
     const size_t lds = (size_t)256 * (size_t)(sc.lane_stack > 0 ? sc.lane_stack : 1) * sizeof(uint32_t) +
-                       ((pn && sc.has_perlin) ? sizeof(PerlinLds) : 0);
-#define RT_FEATURES_F(F)                                                                                    \
-    do {                                                                                                    \
-        if (pn) hipLaunchKernelGGL((k_features<F, true>), dim3(blocks), dim3(256), lds, s, sc, rp, S, feat);  \
-        else hipLaunchKernelGGL((k_features<F, false>), dim3(blocks), dim3(256), lds, s, sc, rp, S, feat);    \
+                       ((tl >= kTexPerlin && sc.has_perlin) ? sizeof(PerlinLds) : 0);
+#define RT_FEATURES_F(F)                                                                                           \
+    do {                                                                                                           \
+        if (tl == kTexImage) hipLaunchKernelGGL((k_features<F, kTexImage>), dim3(blocks), dim3(256), lds, s, sc, rp, S, feat); \
+        else if (tl == kTexPerlin) hipLaunchKernelGGL((k_features<F, kTexPerlin>), dim3(blocks), dim3(256), lds, s, sc, rp, S, feat); \
+        else hipLaunchKernelGGL((k_features<F, kTexPlain>), dim3(blocks), dim3(256), lds, s, sc, rp, S, feat);    \
     } while (0)
     switch (scene_features(sc)) {
     case 0: RT_FEATURES_F(0); break;
@@ -3499,37 +3562,45 @@ hipError_t launch_shade(int mat, const DevScene& sc, const DevScene* scd, const 
     if (blocks > max_blocks) blocks = max_blocks;
     if (blocks == 0u) blocks = kShards;
     const HitRec* hq = hit.h + (size_t)mat * hit.stride;
-#define RT_SHADE_EX(M, PN, LS, EX)                                                                           \
+#define RT_SHADE_EX(M, TL, LS, EX)                                                                           \
     do {                                                                                                     \
         if (ll)                                                                                              \
-            hipLaunchKernelGGL((k_shade<M, PN, LS, true, EX>), dim3(blocks), dim3(256), lds, s, scd, rp, in,   \
+            hipLaunchKernelGGL((k_shade<M, TL, LS, true, EX>), dim3(blocks), dim3(256), lds, s, scd, rp, in,   \
                                hq, qv, out, out_counts, shard_cap, depth);                                   \
         else                                                                                                 \
-            hipLaunchKernelGGL((k_shade<M, PN, LS, false, EX>), dim3(blocks), dim3(256), lds, s, scd, rp, in,  \
+            hipLaunchKernelGGL((k_shade<M, TL, LS, false, EX>), dim3(blocks), dim3(256), lds, s, scd, rp, in,  \
                                hq, qv, out, out_counts, shard_cap, depth);                                   \
     } while (0)
     // libm's own sin / cos for the bounce directions (bounce_cos_sin: RT_OPT_EXACT_LIBM, by default in
     // scenes with curves); only the lambertian kernels draw directions with them
-#define RT_SHADE(M, PN, LS)                                                                                  \
+#define RT_SHADE(M, TL, LS)                                                                                  \
     do {                                                                                                     \
-        if (M == MAT_LAMBERTIAN && rp.exact_libm) RT_SHADE_EX(M, PN, LS, true);                             \
-        else RT_SHADE_EX(M, PN, LS, false);                                                                  \
+        if (M == MAT_LAMBERTIAN && rp.exact_libm) RT_SHADE_EX(M, TL, LS, true);                             \
+        else RT_SHADE_EX(M, TL, LS, false);                                                                  \
     } while (0)
-    const bool pn = sc.has_noise_tex != 0;
+    // the scene's texture level (scenes with image textures take the kTexImage instances, the others keep theirs)
+#define RT_SHADE_TL(M, LS)                                                                                   \
+    do {                                                                                                     \
+        if (tl == kTexImage) RT_SHADE(M, kTexImage, LS);                                                     \
+        else if (tl == kTexPerlin) RT_SHADE(M, kTexPerlin, LS);                                              \
+        else RT_SHADE(M, kTexPlain, LS);                                                                     \
+    } while (0)
+    const int tl = scene_tex_level(sc);
+    const bool pn = tl >= kTexPerlin;
     const bool ls = sc.light.type != LIGHT_OFF;       // only lambertian scatter uses the light mixture
     const size_t leaf_lds = (size_t)sc.n_leaves * sizeof(LeafInfo);
     const bool ll = leaf_lds <= kShadeLeafLds;
-    // PN kernels of every material carry the Perlin tables (metal albedo may be a noise texture)
+    // kTexPerlin / kTexImage kernels of every material carry the Perlin tables (metal albedo may be a noise texture)
     const size_t lds = (ll ? leaf_lds : 0) + ((pn && mat != MAT_DIELECTRIC && sc.has_perlin) ? sizeof(PerlinLds) : 0);
     switch (mat) {
     case MAT_LAMBERTIAN:
-        if (ls) { if (pn) RT_SHADE(MAT_LAMBERTIAN, true, true); else RT_SHADE(MAT_LAMBERTIAN, false, true); }
-        else { if (pn) RT_SHADE(MAT_LAMBERTIAN, true, false); else RT_SHADE(MAT_LAMBERTIAN, false, false); }
+        if (ls) RT_SHADE_TL(MAT_LAMBERTIAN, true); else RT_SHADE_TL(MAT_LAMBERTIAN, false);
         break;
-    case MAT_METAL: if (pn) RT_SHADE(MAT_METAL, true, false); else RT_SHADE(MAT_METAL, false, false); break;
-    case MAT_DIELECTRIC: RT_SHADE(MAT_DIELECTRIC, false, false); break;          // attenuation is constant 1
-    default: if (pn) RT_SHADE(MAT_DIFFUSE_LIGHT, true, false); else RT_SHADE(MAT_DIFFUSE_LIGHT, false, false); break;
+    case MAT_METAL: RT_SHADE_TL(MAT_METAL, false); break;
+    case MAT_DIELECTRIC: RT_SHADE(MAT_DIELECTRIC, kTexPlain, false); break;      // attenuation is constant 1
+    default: RT_SHADE_TL(MAT_DIFFUSE_LIGHT, false); break;
     }
+#undef RT_SHADE_TL
 #undef RT_SHADE
 #undef RT_SHADE_EX
     return hipGetLastError();
@@ -3548,37 +3619,48 @@ hipError_t launch_finish(const DevScene& sc, const DevScene* scd, const RenderPa
     const size_t stack_entry = solo ? sizeof(uint16_t) : sizeof(uint32_t);
     size_t lds = ((size_t)256 * (size_t)(sc.lane_stack > 0 ? sc.lane_stack : 1) * stack_entry + 15) / 16 * 16;
     if (tree0_lds) lds += solo ? tree - (size_t)sc.n_fbleaf * sizeof(BvhLeaf) : tree;
-    // the Perlin tables ride at the end of the dynamic LDS, only where they are staged (PN and tables given)
+    // the Perlin tables ride at the end of the dynamic LDS, only where they are staged (TL >= kTexPerlin and tables given)
     const size_t perlin = sc.has_perlin ? sizeof(PerlinLds) : 0;
     // the bounce directions' sin / cos (RT_OPT_EXACT_LIBM): rt_libm.h's or the device library's
     const bool ex = rp.exact_libm != 0;
-#define RT_FINISH_F(F) RT_FINISH(F, true, true)
-#define RT_FINISH_SOLO_EX(PN, LS, EX) \
-    hipLaunchKernelGGL((k_finish<0, PN, LS, true, EX>), dim3(blocks), dim3(256), lds + (PN ? perlin : 0), s, scd, rp, st, \
+#define RT_FINISH_F(F) do { if (tl == kTexImage) RT_FINISH(F, kTexImage, true); else RT_FINISH(F, kTexPerlin, true); } while (0)
+#define RT_FINISH_SOLO_EX(TL, LS, EX) \
+    hipLaunchKernelGGL((k_finish<0, TL, LS, true, EX>), dim3(blocks), dim3(256), lds + (TL >= kTexPerlin ? perlin : 0), s, scd, rp, st, \
                        in, n, seg_count, tree0_lds, depth)
-#define RT_FINISH_EX(F, PN, LS, EX) \
-    hipLaunchKernelGGL((k_finish<F, PN, LS, false, EX>), dim3(blocks), dim3(256), lds + (PN ? perlin : 0), s, scd, rp, st, \
+#define RT_FINISH_EX(F, TL, LS, EX) \
+    hipLaunchKernelGGL((k_finish<F, TL, LS, false, EX>), dim3(blocks), dim3(256), lds + (TL >= kTexPerlin ? perlin : 0), s, scd, rp, st, \
                        in, n, seg_count, tree0_lds, depth)
-#define RT_FINISH_SOLO(PN, LS) do { if (ex) RT_FINISH_SOLO_EX(PN, LS, true); else RT_FINISH_SOLO_EX(PN, LS, false); } while (0)
-#define RT_FINISH(F, PN, LS) do { if (ex) RT_FINISH_EX(F, PN, LS, true); else RT_FINISH_EX(F, PN, LS, false); } while (0)
+#define RT_FINISH_SOLO(TL, LS) do { if (ex) RT_FINISH_SOLO_EX(TL, LS, true); else RT_FINISH_SOLO_EX(TL, LS, false); } while (0)
+#define RT_FINISH(F, TL, LS) do { if (ex) RT_FINISH_EX(F, TL, LS, true); else RT_FINISH_EX(F, TL, LS, false); } while (0)
+#define RT_FINISH_SOLO_TL(LS) \
+    do { \
+        if (tl == kTexImage) RT_FINISH_SOLO(kTexImage, LS); \
+        else if (tl == kTexPerlin) RT_FINISH_SOLO(kTexPerlin, LS); \
+        else RT_FINISH_SOLO(kTexPlain, LS); \
+    } while (0)
+#define RT_FINISH_TL(LS) \
+    do { \
+        if (tl == kTexImage) RT_FINISH(0, kTexImage, LS); \
+        else if (tl == kTexPerlin) RT_FINISH(0, kTexPerlin, LS); \
+        else RT_FINISH(0, kTexPlain, LS); \
+    } while (0)
     // the plain-sphere feature set also gets Perlin / light-mixture specialisations:
     // the tail kernel carries every material's code, so dropping the unused ones
     // trims its register file
-    const bool pn = sc.has_noise_tex != 0;
+    const int tl = scene_tex_level(sc);
     const bool ls = sc.light.type != LIGHT_OFF;
     switch (scene_features(sc)) {
     case 0:
-        if (solo) {
-            if (pn) { if (ls) RT_FINISH_SOLO(true, true); else RT_FINISH_SOLO(true, false); }
-            else { if (ls) RT_FINISH_SOLO(false, true); else RT_FINISH_SOLO(false, false); }
-        } else if (pn) { if (ls) RT_FINISH(0, true, true); else RT_FINISH(0, true, false); }
-        else { if (ls) RT_FINISH(0, false, true); else RT_FINISH(0, false, false); }
+        if (solo) { if (ls) RT_FINISH_SOLO_TL(true); else RT_FINISH_SOLO_TL(false); }
+        else { if (ls) RT_FINISH_TL(true); else RT_FINISH_TL(false); }
         break;
     case 1: RT_FINISH_F(1); break;
     case 2: RT_FINISH_F(2); break;
     default: RT_FINISH_F(3); break;
     }
 #undef RT_FINISH_F
+#undef RT_FINISH_SOLO_TL
+#undef RT_FINISH_TL
 #undef RT_FINISH_SOLO
 #undef RT_FINISH
 #undef RT_FINISH_SOLO_EX

@@ -102,7 +102,7 @@ int lanes_for(const Context& c, const DevScene& d) {
 
 // The fused curve extend (rt_kernels.hip k_extend_curves<FUSE>: every depth >= 1 of a chunk in one launch)
 // serves curve-kernel scenes whose hits it can shade itself: no Perlin tables (the fused kernel keeps no
-// LDS copy of them) and no light mixture (f2).  It pays where the per-depth launches are small: each
+// LDS copy of them), no image textures (it carries no u, v) and no light mixture (f2).  It pays where the per-depth launches are small: each
 // persistent launch drains once (~1.1 ms at C5), which a depth-1 launch of n rays amortises over n.  C5,
 // fused vs one launch per depth (profiles/r05/ab/fuse/): 1 spp 275.2 vs 189.5 Mrays/s, 8 spp 380.4 vs
 // 356.1, 32 spp 394.8 vs 395.8, 256 spp (128-spp chunks) 402.9 vs 407.8 — so it is taken for depth-1
@@ -111,7 +111,7 @@ int lanes_for(const Context& c, const DevScene& d) {
 // (2^23 / 2^25: the same within noise at 32 and 256 spp, profiles/r06/fuse_max/)
 constexpr uint32_t kFuseMaxRays = 1u << 24;
 bool curve_fuse(const DevScene& d, const uint32_t n) {
-    if (!(curve_kernel_scene(d) && curve_persistent() && !d.has_perlin && d.light.type == LIGHT_OFF)) return false;
+    if (!(curve_kernel_scene(d) && curve_persistent() && !d.has_perlin && !d.has_image_tex && d.light.type == LIGHT_OFF)) return false;
     if (!d.fuse_ring || d.n_leaves >= (1 << kFuseLeafBits) - 1) return false;    // FuseHit packs leaf + 1 in 25 bits
     const char* e = std::getenv("RTAMD_CURVE_FUSE");   // read per render: tests switch it inside one process
     if (e && e[0] == '0') return false;

@@ -171,6 +171,27 @@ static int add_scaled_tex(int scene, int type, double sc, int* out) {
 }
 int rt_add_texture_noise(int scene, double sc, int* out) { return add_scaled_tex(scene, TEX_NOISE, sc, out); }
 int rt_add_texture_marble(int scene, double sc, int* out) { return add_scaled_tex(scene, TEX_MARBLE, sc, out); }
+// t:image-texture (texture.scm:36-50; include/rt.h, "image textures"): the bytes packed one dword per texel
+// into the scene's texel array (uploaded at commit), the texture record holding its offset and size
+int rt_add_texture_image(int scene, const uint8_t* rgb, int nx, int ny, int* out) {
+    // the arguments first, so they are refused whatever the handle is
+    OUT_OR_FAIL(out);
+    if (!rgb) return fail("rt_add_texture_image: null texel pointer");
+    if (nx < 1 || ny < 1) return fail("rt_add_texture_image: nx and ny must be at least 1");
+    const uint64_t n = (uint64_t)nx * (uint64_t)ny;
+    if (n > (1ull << 26)) return fail("rt_add_texture_image: at most 2^26 texels per image");
+    SCENE_OR_FAIL(s, scene);
+    if (s->teximg.size() + n > 0x7fffffffull) return fail("rt_add_texture_image: the scene's images exceed 2^31 - 1 texels");
+    DevTexture t{};
+    t.type = TEX_IMAGE; t.a = nx; t.b = ny; t.off = (int32_t)s->teximg.size();
+    s->teximg.resize(s->teximg.size() + (size_t)n);
+    uint32_t* dst = s->teximg.data() + (size_t)t.off;
+    for (size_t k = 0; k < (size_t)n; ++k)
+        dst[k] = (uint32_t)rgb[3 * k] | (uint32_t)rgb[3 * k + 1] << 8 | (uint32_t)rgb[3 * k + 2] << 16;
+    s->texs.push_back(t);
+    *out = (int)s->texs.size() - 1;
+    return 0;
+}
 
 static int add_mat(int scene, int type, int tex, double fuzz, double ref, int* out) {
     SCENE_OR_FAIL(s, scene);

@@ -101,6 +101,7 @@ _SIGNATURES = {
     "rt_add_texture_checker": [ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_int_p],
     "rt_add_texture_noise": [ctypes.c_int, ctypes.c_double, _c_int_p],
     "rt_add_texture_marble": [ctypes.c_int, ctypes.c_double, _c_int_p],
+    "rt_add_texture_image": [ctypes.c_int, _c_u8_p, ctypes.c_int, ctypes.c_int, _c_int_p],    # RT_HAS_IMAGE_TEXTURE
     "rt_add_material_lambertian": [ctypes.c_int, ctypes.c_int, _c_int_p],
     "rt_add_material_metal": [ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_int_p],
     "rt_add_material_dielectric": [ctypes.c_int, ctypes.c_double, _c_int_p],

@@ -106,6 +106,13 @@ class GpuBuilder:
     def texture_marble(self, sc):
         return self._out("rt_add_texture_marble", sc)
 
+    def texture_image(self, data, nx, ny):
+        """data: contiguous uint8 array of nx*ny*3 (row 0 = top); the library copies it."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if data.size != nx * ny * 3:
+            raise ValueError("image texture data must have nx*ny*3 bytes")
+        return self._out("rt_add_texture_image", data.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), int(nx), int(ny))
+
     def material_lambertian(self, tex):
         return self._out("rt_add_material_lambertian", tex)
 

@@ -46,6 +46,17 @@ def marble_texture(sc):
     return Texture("marble", float(sc))
 
 
+def make_image_texture(data, nx, ny):
+    """t:image-texture (texture.scm:36-50): ``data`` is bytes or a uint8 array
+    of nx*ny*3 (r, g, b per texel, row 0 first = the top of the image, v = 1).
+    The lookup and the hit records' u, v are stated in include/rt.h ("image
+    textures") and restated in rtamd.image; the reference's own `data` may hold
+    any numbers under floor->exact, this takes bytes."""
+    from .image import as_texels
+    nx, ny = int(nx), int(ny)
+    return Texture("image", as_texels(data, nx, ny).copy(), nx, ny)
+
+
 # ---------------------------------------------------------------- materials
 
 
@@ -298,7 +309,7 @@ def _need(x, cls, what):
 def emit(scene, b):
     """Replay the scene's descriptor graph into builder ``b`` and commit it.
 
-    ``b`` provides texture_*/material_*/sphere/moving_sphere/rect/
+    ``b`` provides texture_* (texture_image: the GPU builder only)/material_*/sphere/moving_sphere/rect/
     flip_normals/box/translate/rotate_y/list/bvh/set_camera/set_sky/
     set_perlin/commit (see GpuBuilder).  Returns b.commit(world)'s value.
     """
@@ -316,6 +327,11 @@ def emit(scene, b):
                 memo[k] = b.texture_noise(t.args[0])
             elif t.kind == "marble":
                 memo[k] = b.texture_marble(t.args[0])
+            elif t.kind == "image":
+                if not hasattr(b, "texture_image"):
+                    raise NotImplementedError(
+                        "image textures are not restated in %s (only the GPU builder takes them)" % type(b).__name__)
+                memo[k] = b.texture_image(t.args[0], t.args[1], t.args[2])
             else:
                 raise ValueError(t.kind)
         return memo[k]

@@ -132,6 +132,51 @@ def cornell_box(nx, ny):
     return g.make_scene(objs, cornell_camera_for(nx, ny), g.sky_color)
 
 
+def cornell_image_textures(floor_size=(64, 64), wall_size=(32, 32)):
+    """cornell_image's two images, generated from formulas: the floor a grid of warm tiles with dark joints,
+    the back wall a smooth two-way colour ramp.  Returns (floor, wall) image textures."""
+    import numpy as np
+
+    def grid(size):
+        nx, ny = size
+        y, x = np.mgrid[0:ny, 0:nx]
+        return x, y, np.zeros((ny, nx, 3), dtype=np.uint8)
+
+    x, y, floor = grid(floor_size)
+    joint = ((x % 8) == 0) | ((y % 8) == 0)
+    tile = ((x // 8) + (y // 8)) % 2
+    floor[..., 0] = np.where(joint, 40, 150 + 60 * tile)
+    floor[..., 1] = np.where(joint, 40, 120 + 50 * tile)
+    floor[..., 2] = np.where(joint, 40, 90 + 40 * tile)
+    x, y, wall = grid(wall_size)
+    wall[..., 0] = 30 + (200 * x) // max(1, wall_size[0] - 1)
+    wall[..., 1] = 30 + (200 * y) // max(1, wall_size[1] - 1)
+    wall[..., 2] = 180 - (100 * ((x + y) % 4)) // 3
+    return (g.make_image_texture(floor, floor_size[0], floor_size[1]),
+            g.make_image_texture(wall, wall_size[0], wall_size[1]))
+
+
+def cornell_image(nx, ny, floor_size=(64, 64), wall_size=(32, 32)):
+    """cornell-box (main.scm:330-351) with an image texture (t:image-texture, texture.scm:36-50) on the
+    floor and on the back wall; everything else as cornell_box."""
+    floor_tex, wall_tex = cornell_image_textures(floor_size, wall_size)
+    red = g.make_lambertian(g.constant_texture(v.vec3(0.65, 0.05, 0.05)))
+    white = g.make_lambertian(g.constant_texture(v.vec3(0.73, 0.73, 0.73)))
+    green = g.make_lambertian(g.constant_texture(v.vec3(0.12, 0.45, 0.15)))
+    light = g.make_diffuse_light(g.constant_texture(v.vec3(3, 3, 3)))
+    objs = [
+        g.flip_normals(g.make_yz_rect(0, 555, 0, 555, 555, green)),
+        g.make_yz_rect(0, 555, 0, 555, 0, red),
+        g.flip_normals(g.make_xz_rect(213, 343, 227, 332, 554, light)),
+        g.flip_normals(g.make_xz_rect(0, 555, 0, 555, 555, white)),
+        g.make_xz_rect(0, 555, 0, 555, 0, g.make_lambertian(floor_tex)),
+        g.flip_normals(g.make_xy_rect(0, 555, 0, 555, 555, g.make_lambertian(wall_tex))),
+        g.translate(g.rotate_y(g.make_box(v.vec3(0, 0, 0), v.vec3(165, 165, 165), white), -18), v.vec3(130, 0, 65)),
+        g.translate(g.rotate_y(g.make_box(v.vec3(0, 0, 0), v.vec3(165, 330, 165), white), 15), v.vec3(265, 0, 295)),
+    ]
+    return g.make_scene(objs, cornell_camera_for(nx, ny), g.sky_color)
+
+
 def cornell_mixture(nx, ny):
     """cornell-box with the pdf.scm mixture (extension f2, config C4's
     "mixture/cosine importance sampling"): lambertian bounces sample the
@@ -311,6 +356,7 @@ SCENES = {
     "cornell_bezier": cornell_bezier,
     "cornell_smoke": cornell_smoke,
     "cornell_mixture": cornell_mixture,
+    "cornell_image": cornell_image,
     "klein": klein_scene,
     "cornell_klein": cornell_klein,
     "curves": cornell_curves,
