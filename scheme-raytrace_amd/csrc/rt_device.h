@@ -126,17 +126,13 @@ struct DevCamera {            // camera.scm:33-78 (the 10 slots)
     double lens, t0, t1;
 };
 
+constexpr int kBezRing = 256;                  // survivor ring entries per wave (> the survivors a wave holds)
+constexpr int kCurveWaves = 2;                 // waves per SIMD k_extend_curves is compiled for (VGPR budget 512 / waves)
 // k_extend_curves' BVH4 stack entries per lane in LDS (the rest of a deep walk's stack goes to the
 // overflow area).  15 is the most that keeps two 256-thread blocks (the register-bound occupancy) on a
 // 160-KiB CU beside the blocks' BezWave state; C5 at 8 spp: 8 -> 320, 12 -> 337, 15 -> 340 Mrays/s
 // (profiles/r04/ab_stack.log)
-constexpr int kBezRing = 256;                  // survivor ring entries per wave (> the survivors a wave holds)
-#ifndef RT_CURVE_WAVES
-#define RT_CURVE_WAVES 2               // waves per SIMD k_extend_curves is compiled for (VGPR budget 512 / waves)
-#endif
-#ifndef RT_CURVE_LDS_STACK
-#define RT_CURVE_LDS_STACK 15
-#endif
+constexpr int kCurveLdsStack = 15;
 
 struct DevScene {
     const SphereRec* sph;  int32_t n_sph;
@@ -252,10 +248,7 @@ constexpr int kShards = 8;
 // Counter k of a counter array lives at [k * kCntStride] (uint32 units): each
 // shard counter gets its own 128-B line, so the shards' atomics do not meet
 // in one L2 line.
-#ifndef RT_CNT_STRIDE
-#define RT_CNT_STRIDE 32
-#endif
-constexpr int kCntStride = RT_CNT_STRIDE;
+constexpr int kCntStride = 32;
 struct QView { const uint32_t* counts; uint32_t cap; };
 
 // The fused curve extend's hand-off records (DevScene::fuse_ring).  A lane whose ray is resolved parks

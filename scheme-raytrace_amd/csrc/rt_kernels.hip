@@ -387,9 +387,6 @@ __device__ __forceinline__ bool bez_culled(const Bez4& c, const double w1, const
 // from the exact sub-curves by a few ulps of their magnitude s per level (and
 // bez-p by a few more), so r = width1 (1 + 1e-9) + 1e-9 s keeps the cull
 // conservative by orders of magnitude; NaNs and a zero edge never cull.
-#ifndef RT_BEZ_HULL
-#define RT_BEZ_HULL 1
-#endif
 __device__ __forceinline__ bool bez_sep_axis(const Bez4& c, const v3 a, const v3 b, const double r2) {
     const double nx = a.y - b.y, ny = b.x - a.x;                 // normal of the edge a -> b
     const double d0 = fma(c.p0.x, nx, c.p0.y * ny), d1 = fma(c.p1.x, nx, c.p1.y * ny);
@@ -413,7 +410,6 @@ __device__ __forceinline__ double bez_hull_r2(const Bez4& c, const double w1) {
 }
 template <int EDGES>
 __device__ __forceinline__ bool bez_hull_sep(const Bez4& c, const double r2) {
-    if (!RT_BEZ_HULL) return false;
     bool sep = bez_sep_axis(c, c.p0, c.p3, r2);
     if (EDGES > 1)
         sep = sep || bez_sep_axis(c, c.p0, c.p1, r2) || bez_sep_axis(c, c.p1, c.p2, r2) || bez_sep_axis(c, c.p2, c.p3, r2);
@@ -421,7 +417,7 @@ __device__ __forceinline__ bool bez_hull_sep(const Bez4& c, const double r2) {
 }
 template <int EDGES>
 __device__ __forceinline__ bool bez_hull_culled(const Bez4& c, const double w1) {
-    return RT_BEZ_HULL && bez_hull_sep<EDGES>(c, bez_hull_r2(c, w1));
+    return bez_hull_sep<EDGES>(c, bez_hull_r2(c, w1));
 }
 // converge's box cull plus the hull cull
 template <int EDGES>
@@ -459,7 +455,7 @@ __device__ __forceinline__ bool bez_culled_hull(const Bez4& c, const double w1, 
 // bez_walk_node (a pending right sibling re-derived in one go, then split)
 // and bez_walk_leaf (a leaf segment's test).  Stage B calls node / leaf, and
 // holds lanes at leaf segments until enough of them test together
-// (RT_BEZ_LEAF_PHASE); the per-lane bezier_test calls split / leaf.
+// (kBezLeafPhase); the per-lane bezier_test calls split / leaf.
 // RING (k_extend_curves' stage B): the root is not held in registers — the walk re-reads it from the
 // survivor's ring line when it re-derives a node (24 VGPRs less at the kernel's peak)
 template <bool RING> struct BezRootOf { Bez4 root; };
@@ -571,11 +567,11 @@ __device__ __forceinline__ bool bez_walk_split(BezWalkT<RING>& s, Bez4* slot = n
 }
 // one node (not at a leaf): a pending right sibling is re-derived from the
 // root in one go, then split; true once the walk is over
-template <bool SLOT = false, bool RING = false>
-__device__ __forceinline__ bool bez_walk_node(BezWalkT<RING>& s, Bez4* slot = nullptr) {
+template <bool RING>
+__device__ __forceinline__ bool bez_walk_node(BezWalkT<RING>& s, Bez4* slot) {
     if (!s.fresh) {
         if (++s.it > s.cap + 1u) { raise_fault(RT_FAULT_CURVE); return true; }
-        if (SLOT && s.pl == s.L) {                              // the pending sibling kept in the slot
+        if (s.pl == s.L) {                              // the pending sibling kept in the slot
             s.c = *slot;
             s.pl = -1;
         } else {
@@ -591,7 +587,7 @@ __device__ __forceinline__ bool bez_walk_node(BezWalkT<RING>& s, Bez4* slot = nu
         s.fresh = true;
         if (s.L >= s.leaf_level) return false;                  // a leaf: tested in a leaf phase
     }
-    return bez_walk_split<SLOT>(s, slot);
+    return bez_walk_split<true>(s, slot);
 }
 // the leaf segment's test (:130-166) (bez_walk_at_leaf); true once the walk is over
 template <bool RING>
@@ -691,18 +687,54 @@ __device__ __forceinline__ bool bezier_test(const BezierRec& B, const BezRay& R,
     return true;
 }
 
+// Statistics (the RT_STATS build only; rt_debug_stats reads and clears them).  The slot numbers are what
+// tools/trav_stats.py (T) and tools/curve_stats.py (C) index with: they do not move.
+enum StatSlot {
+    // bvh_closest_lane, the all-times tree (T); kStatTree0 + the same offsets: the time-0 tree (T)
+    kStatRays = 0, kStatNodes, kStatLeaves, kStatSpheres, kStatMSpheres, kStatInner, kStatOuter,   // per lane
+    kStatWaves, kStatWaveInner, kStatWaveOuter, kStatLanes,      // per wave: the slowest lane's iterations, active lanes
+    // bvh_closest_curves and the batches every curve walk runs (T, C)
+    kStatCurveRays = 11, kStatCurveNodes, kStatCurveLeaves, kStatCurveCands,
+    kStatCurveSurvivors = 15,                                    // bez_stage_a: root-cull survivors
+    // Slots 16..26 have two writers: the time-0 walk (kStatTree0 + 0..10) and, in scenes with curves (which
+    // have no time-0 walk), k_extend_curves at 20..25 (T, C).  A scene is one or the other.
+    kStatTree0 = 16,
+    kStatKcSteps = 20, kStatKcBusy, kStatKcWait,                 // k_extend_curves, lane-iterations: BVH step, busy, waiting
+    kStatKcIters = 23, kStatKcWaves, kStatKcFlushes,             // per wave
+    kStatCurveFlushes = 27, kStatCurveIters, kStatCurveWaves, kStatCurveLanes,   // bvh_closest_curves, per wave (T)
+    // bez_stage_b (C): passes, wave iterations, busy lane-iterations, walk steps, re-derived nodes,
+    // re-derivation splits, leaf tests, survivors
+    kStatBPasses = 31, kStatBIters, kStatBBusy, kStatBSteps, kStatBRederived, kStatBResplits, kStatBLeafTests,
+    kStatBSurvivors = 38,
+    // clocks (s_memtime of one lane per wave) (C): stage B; k_extend_curves whole / stage A / steps 1-3;
+    // stage B's refill and donation rounds / leaf tests / node steps
+    kStatBClock = 39, kStatKcClock, kStatKcClockA, kStatKcClock1, kStatKcClock2, kStatKcClock3,
+    kStatBClockRefill = 45, kStatBClockLeaf, kStatBClockNode,
+    kStatSlots = 48
+};
+// StatCount / StatClock: a counter or clock sum a kernel keeps in a register, declared and bumped alike in
+// both builds: an integer in the stats build, nothing in the product
 #ifdef RT_STATS
-// traversal statistics (stats builds only): rays, node visits, leaf visits,
-// sphere tests, moving-sphere tests, lane inner / outer loop iterations,
-// waves, wave-max inner / outer iterations, lanes; [0..10] all-times tree,
-// [16..26] time-0 tree; curve trees: [11] rays, [12] node visits, [13] leaf
-// visits, [14] queued curve candidates, [15] root-cull survivors, [27] flushes,
-// [28] wave loop iterations, [29] waves, [30] lanes
-__device__ unsigned long long g_stats[48];
-#define RT_STAT(k, v) atomicAdd(&g_stats[k], (unsigned long long)(v))
+constexpr bool kStats = true;
+__device__ unsigned long long g_stats[kStatSlots];
+__device__ __forceinline__ void stat_add(const int k, const unsigned long long v) { atomicAdd(&g_stats[k], v); }
+using StatCount = uint32_t;
+using StatClock = unsigned long long;
 #else
-#define RT_STAT(k, v) ((void)0)
+constexpr bool kStats = false;
+__device__ __forceinline__ void stat_add(int, unsigned long long) {}
+struct StatNone {
+    __device__ __forceinline__ void operator++() {}
+    __device__ __forceinline__ void operator+=(unsigned long long) {}
+    __device__ __forceinline__ operator unsigned long long() const { return 0; }
+};
+using StatCount = StatNone;
+using StatClock = StatNone;
 #endif
+__device__ __forceinline__ unsigned long long stat_clock() {
+    if constexpr (kStats) return __builtin_amdgcn_s_memtime();
+    else return 0ull;
+}
 
 // ------------------------------------------------- curve candidate batching
 // Curve tests are long and their length varies per (ray, curve), so testing
@@ -717,40 +749,21 @@ __device__ unsigned long long g_stats[48];
 // curve's answer does not depend on the t-max it is tested with, beyond
 // being reported only when z <= t-max (see bezier_test), so deferring the
 // tests changes no result.
-#ifndef RT_BEZ_REFILL
-#define RT_BEZ_REFILL 8
-#endif
-constexpr int kBezRefill = RT_BEZ_REFILL;   // stage B: idle lanes that take the next survivors together
-#ifndef RT_BEZ_DONATE
-#define RT_BEZ_DONATE 16               // stage B: idle lanes (at least) that take pending subtrees together (0 = none)
-#endif
-#ifndef RT_BEZ_WAIT_FLUSH
-#define RT_BEZ_WAIT_FLUSH 0            // k_extend_curves: lanes waiting on their curves that force a batch (0 = off)
-#endif
-#ifndef RT_BEZ_SLOT
-#define RT_BEZ_SLOT 1                  // stage B: an LDS slot per lane for its latest pending right sibling
-#endif
-#ifndef RT_BEZ_QFLUSH
-#define RT_BEZ_QFLUSH 48               // k_extend_curves: queued candidates that trigger a batch (stage A)
-#endif
-constexpr int kBezQ = (RT_BEZ_QFLUSH > 64 ? RT_BEZ_QFLUSH : 64) + 64;   // < the trigger before a step, + 1 per lane per step
-#ifndef RT_BEZ_HOLD
-#define RT_BEZ_HOLD 64                 // stage B runs once this many root-cull survivors wait (multiple of 64)
-#endif
-#ifndef RT_BEZ_LEAF_PHASE
-#define RT_BEZ_LEAF_PHASE 40           // stage B: lanes at a leaf segment that test together
-#endif
-#ifndef RT_CURVE_FINISH_BATCH
-#define RT_CURVE_FINISH_BATCH 20       // k_extend_curves: finished lanes written out and refilled together
-#endif
-constexpr int kBezS = RT_BEZ_HOLD + kBezQ;   // survivors: < RT_BEZ_HOLD carried over + one stage A's worth
+// Frozen by measurement ("Curves"): each value is the winner of a closed A/B.
+constexpr int kBezRefill = 8;          // stage B: idle lanes that take the next survivors together
+constexpr int kBezDonate = 16;         // stage B: idle lanes (at least) that take pending subtrees together
+constexpr int kBezQFlush = 48;         // k_extend_curves: queued candidates that trigger a batch (stage A)
+constexpr int kBezHold = 64;           // stage B runs once this many root-cull survivors wait (multiple of 64)
+constexpr int kBezLeafPhase = 40;      // stage B: lanes at a leaf segment that test together
+constexpr int kCurveFinishBatch = 20;  // k_extend_curves: finished lanes written out and refilled together
+constexpr int kBezQ = (kBezQFlush > 64 ? kBezQFlush : 64) + 64;   // < the trigger before a step, + 1 per lane per step
+constexpr int kBezS = kBezHold + kBezQ;   // survivors: < kBezHold carried over + one stage A's worth
 static_assert(kBezS <= kBezRing && (kBezRing & (kBezRing - 1)) == 0,
               "k_extend_curves' survivor ring holds every survivor a wave can hold (slot = rtail + position)");
+static_assert(kFuseRing >= 2 * 64, "k_extend_curves' hand-off rings: a shading round's 64 entries beside the 64 a wave can add");
 static_assert(2 * 64 <= kBezQ, "stage B's donation handover: two words per donor lane in W.q");
 static_assert(kBezMaxDepth + 1 < 26, "the handover packs a level (6 bits) above a node index (26 bits)");
-template <bool SLOT_>
-struct BezWaveT {
-    static constexpr bool SLOT = SLOT_;
+struct BezWave {
     BezRay ray[64];                 // owner lane's ray-space matrix
     double cl[64];                  // owner's closest t when a batch runs
     double hz[64];                  // owner's best curve z from the batch
@@ -759,10 +772,9 @@ struct BezWaveT {
     uint32_t sv[kBezS];             // root-test survivors waiting for subdivision
     double sz[kBezS];               // their results (z or +inf)
     uint32_t done[64];              // persistent kernel: owner's candidates resolved so far
-    Bez4 pend[SLOT_ ? 64 : 1];      // stage B: each lane's latest pending right sibling (bez_walk_split)
+    Bez4 pend[64];                  // stage B: each lane's latest pending right sibling (bez_walk_split)
     uint8_t lev[kBezS];             // survivors' subdivision leaf levels (stage A)
 };
-using BezWave = BezWaveT<RT_BEZ_SLOT != 0>;
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -772,8 +784,8 @@ __device__ __forceinline__ void wave_sync() {
 // the survivor list (svn entries already there).  Returns the new count.
 // Every active lane calls it with the same arguments.
 // TRACK (k_extend_curves): survivors also go to the wave's ring (slot rtail + position, mod kBezRing)
-template <bool TRACK = false, class WV = BezWave>
-__device__ __forceinline__ uint32_t bez_stage_a(const DevScene& sc, WV& W, const uint32_t qn, uint32_t svn,
+template <bool TRACK = false>
+__device__ __forceinline__ uint32_t bez_stage_a(const DevScene& sc, BezWave& W, const uint32_t qn, uint32_t svn,
                                                 BezRoot* __restrict__ ring = nullptr, const uint32_t rtail = 0u) {
     const unsigned long long act = __ballot(1);
     const uint32_t nact = (uint32_t)__popcll(act), rank = lanes_below(act);
@@ -807,9 +819,7 @@ __device__ __forceinline__ uint32_t bez_stage_a(const DevScene& sc, WV& W, const
             }
         }
         svn += (uint32_t)__popcll(m);
-#ifdef RT_STATS
-        if (rank == 0) RT_STAT(15, __popcll(m));
-#endif
+        if (rank == 0) stat_add(kStatCurveSurvivors, __popcll(m));
     }
     wave_sync();
     return svn;
@@ -819,17 +829,17 @@ __device__ __forceinline__ uint32_t bez_stage_a(const DevScene& sc, WV& W, const
 // owner the smallest z (ties: the later curve of the list) into hz / hkey; the
 // remaining svn - nb survivors move to the front.
 // Pooled-curve counters (rt_stats.curve_pooled_batches / curve_flat_pooled):
-// stage B passes over a full pool (>= RT_BEZ_HOLD survivors), and the
+// stage B passes over a full pool (>= kBezHold survivors), and the
 // survivors they walked whose root is already a leaf (a flat curve: converge's
 // depth estimate is negative, bezier.scm:130,189-193).  One atomic per pass;
 // read and cleared by take_curve_stats.
 __device__ unsigned long long g_curve_stats[2];
-template <bool TRACK = false, class WV = BezWave>
-__device__ __forceinline__ void bez_stage_b(const DevScene& sc, WV& W, const uint32_t nb, const uint32_t svn,
+template <bool TRACK = false>
+__device__ __forceinline__ void bez_stage_b(const DevScene& sc, BezWave& W, const uint32_t nb, const uint32_t svn,
                                             const BezRoot* __restrict__ ring = nullptr, const uint32_t rtail = 0u) {
     const unsigned long long act = __ballot(1);
     const uint32_t nact = (uint32_t)__popcll(act), rank = lanes_below(act);
-    if (nb >= (uint32_t)RT_BEZ_HOLD) {
+    if (nb >= (uint32_t)kBezHold) {
         uint32_t flat = 0;
         for (uint32_t base = 0; base < nb; base += nact)
             flat += (uint32_t)__popcll(__ballot(base + rank < nb && W.lev[base + rank] == 0));
@@ -850,29 +860,24 @@ __device__ __forceinline__ void bez_stage_b(const DevScene& sc, WV& W, const uin
         BezWalkT<TRACK> wk;
         bool busy = false;
         uint32_t si = 0, cursor = 0;
-#ifdef RT_STATS
-        // [31] passes [32] wave iterations [33] busy lane-iterations [34] walk steps [35] re-derived
-        // nodes [36] re-derivation splits [37] leaf tests [38] survivors [39] stage B clock (lane 0)
-        uint32_t n_it = 0, n_busy = 0, n_step = 0, n_red = 0, n_rsplit = 0, n_leaf = 0;
-        unsigned long long n_clk_refill = 0;          // [45] stage B clock in refill / donation rounds (lane 0)
-        unsigned long long n_clk_leaf = 0, n_clk_node = 0;   // [46] leaf tests, [47] node steps (splits, re-derivation)
-        const unsigned long long clk0 = __builtin_amdgcn_s_memtime();
-#endif
+        // (this loop's and k_extend_curves' statistics sit under if constexpr: there even statements that
+        // compile to nothing move the product build's register allocation)
+        StatCount n_it{}, n_busy{}, n_step{}, n_red{}, n_rsplit{}, n_leaf{};
+        StatClock n_clk_refill{}, n_clk_leaf{}, n_clk_node{};   // refill / donation rounds, leaf tests, node steps (splits, re-derivation)
+        const unsigned long long clk0 = stat_clock();
         const unsigned long long guard_cap = (unsigned long long)(nb + 2u) * (((unsigned long long)(kBezMaxDepth + 3) << (kBezMaxDepth + 2)) + 2ull);
         for (unsigned long long g = 0;; ++g) {                    // wave-uniform
             if (g > guard_cap) { raise_fault(RT_FAULT_CURVE); break; }
-#ifdef RT_STATS
-            ++n_it;
-            n_busy += busy ? 1u : 0u;
-            if (busy) {
-                ++n_step;
-                if (!wk.fresh) { ++n_red; n_rsplit += (uint32_t)wk.L; }
-                if (bez_walk_at_leaf(wk)) ++n_leaf;     // lane-iterations at a leaf (tested or waiting)
+            if constexpr (kStats) {
+                ++n_it;
+                n_busy += busy ? 1u : 0u;
+                if (busy) {
+                    ++n_step;
+                    if (!wk.fresh) { ++n_red; n_rsplit += (uint32_t)wk.L; }
+                    if (bez_walk_at_leaf(wk)) ++n_leaf;     // lane-iterations at a leaf (tested or waiting)
+                }
             }
-#endif
-#ifdef RT_STATS
-            const unsigned long long cr0 = __builtin_amdgcn_s_memtime();
-#endif
+            const unsigned long long cr0 = stat_clock();
             const unsigned long long idle = __ballot(!busy);
             if (cursor < nb && (__popcll(idle) >= kBezRefill || idle == act)) {
                 if (!busy) {
@@ -888,7 +893,7 @@ __device__ __forceinline__ void bez_stage_b(const DevScene& sc, WV& W, const uin
                     }
                 }
                 cursor += (uint32_t)__popcll(idle);
-            } else if (RT_BEZ_DONATE > 0 && cursor >= nb && __popcll(idle) >= RT_BEZ_DONATE && idle != act) {
+            } else if (cursor >= nb && __popcll(idle) >= kBezDonate && idle != act) {
                 // donation round: the candidate queue is empty during stage B, W.q carries the handover
                 const uint32_t pend = busy ? bez_walk_pending(wk) : 0u;
                 const unsigned long long dm = __ballot(pend != 0u);
@@ -916,9 +921,7 @@ __device__ __forceinline__ void bez_stage_b(const DevScene& sc, WV& W, const uin
                     wave_sync();
                 }
             }
-#ifdef RT_STATS
-            n_clk_refill += __builtin_amdgcn_s_memtime() - cr0;
-#endif
+            if constexpr (kStats) n_clk_refill += stat_clock() - cr0;
             const unsigned long long bm = __ballot(busy);
             if (bm == 0ull) {
                 if (cursor >= nb) break;
@@ -929,32 +932,22 @@ __device__ __forceinline__ void bez_stage_b(const DevScene& sc, WV& W, const uin
             const bool at_leaf = busy && bez_walk_at_leaf(wk);
             const unsigned long long lm = __ballot(at_leaf);
             bool over = false;
-#ifdef RT_STATS
-            const unsigned long long cl0 = __builtin_amdgcn_s_memtime();
-#endif
-            if (lm != 0ull && (__popcll(lm) >= RT_BEZ_LEAF_PHASE || lm == bm)) {
+            const unsigned long long cl0 = stat_clock();
+            if (lm != 0ull && (__popcll(lm) >= kBezLeafPhase || lm == bm)) {
                 if (at_leaf) over = bez_walk_leaf(wk);
             }
-#ifdef RT_STATS
-            const unsigned long long cl1 = __builtin_amdgcn_s_memtime();
-            n_clk_leaf += cl1 - cl0;
-#endif
-            if constexpr (WV::SLOT) {
-                if (busy && !at_leaf) over = bez_walk_node<true>(wk, &W.pend[threadIdx.x & 63u]);
-            } else {
-                if (busy && !at_leaf) over = bez_walk_node(wk);
-            }
-#ifdef RT_STATS
-            n_clk_node += __builtin_amdgcn_s_memtime() - cl1;
-#endif
+            const unsigned long long cl1 = stat_clock();
+            if constexpr (kStats) n_clk_leaf += cl1 - cl0;
+            if (busy && !at_leaf) over = bez_walk_node(wk, &W.pend[threadIdx.x & 63u]);
+            if constexpr (kStats) n_clk_node += stat_clock() - cl1;
             if (over) {
                 if (wk.found)
                     atomicMin((unsigned long long*)&W.sz[si], (unsigned long long)__double_as_longlong(wk.best));
                 busy = false;
             }
         }
-#ifdef RT_STATS
-        {   // per-lane counts summed in LDS first: 64 global atomics per counter and pass would load stage B itself
+        if constexpr (kStats) {
+            // per-lane counts summed in LDS first: 64 global atomics per counter and pass would load stage B itself
             __shared__ unsigned int s_st[4][5];
             unsigned int* ws = s_st[(threadIdx.x >> 6) & 3u];
             for (uint32_t j = rank; j < 5u; j += nact) ws[j] = 0u;
@@ -963,16 +956,16 @@ __device__ __forceinline__ void bez_stage_b(const DevScene& sc, WV& W, const uin
             atomicAdd(&ws[3], n_rsplit); atomicAdd(&ws[4], n_leaf);
             wave_sync();
             if (rank == 0) {
-                RT_STAT(33, ws[0]); RT_STAT(34, ws[1]); RT_STAT(35, ws[2]); RT_STAT(36, ws[3]); RT_STAT(37, ws[4]);
+                stat_add(kStatBBusy, ws[0]); stat_add(kStatBSteps, ws[1]); stat_add(kStatBRederived, ws[2]);
+                stat_add(kStatBResplits, ws[3]); stat_add(kStatBLeafTests, ws[4]);
             }
             wave_sync();
+            if (rank == 0) {
+                stat_add(kStatBPasses, 1); stat_add(kStatBIters, n_it); stat_add(kStatBSurvivors, nb);
+                stat_add(kStatBClock, stat_clock() - clk0); stat_add(kStatBClockRefill, n_clk_refill);
+                stat_add(kStatBClockLeaf, n_clk_leaf); stat_add(kStatBClockNode, n_clk_node);
+            }
         }
-        if (rank == 0) {
-            RT_STAT(31, 1); RT_STAT(32, n_it); RT_STAT(38, nb);
-            RT_STAT(39, __builtin_amdgcn_s_memtime() - clk0); RT_STAT(45, n_clk_refill);
-            RT_STAT(46, n_clk_leaf); RT_STAT(47, n_clk_node);
-        }
-#endif
     }
     wave_sync();
     for (uint32_t base = 0; base < nb; base += nact) {
@@ -1006,8 +999,7 @@ __device__ __forceinline__ void bez_stage_b(const DevScene& sc, WV& W, const uin
 // takes the hit on a tie with a sphere or rect; between two curves at the
 // same z the later one of the list (BezierRec::order) is the one the scan
 // keeps, whichever batch tested it first.
-template <class WV>
-__device__ __forceinline__ void bez_take_batch(const DevScene& sc, const WV& W, const uint32_t lane,
+__device__ __forceinline__ void bez_take_batch(const DevScene& sc, const BezWave& W, const uint32_t lane,
                                                const int32_t bz, double& closest, int32_t& best) {
     const double z = W.hz[lane];
     if (z == INFINITY || z > closest) return;
@@ -1098,15 +1090,12 @@ __device__ __forceinline__ void node_hit(const BvhNode2& N, const BoxRayW& r, co
     hr = one(1, tr);
 }
 
-// Sign-selected slab planes (RT_SIGNED_SLAB, the LDS-tree walks): with the
+// Sign-selected slab planes (the time-0 LDS-tree walks): with the
 // sign of 1/d known per lane, an axis's near plane is its lo plane for a
 // positive component and its hi plane otherwise (fma(b, 1/d, -o/d) rounds
 // monotonically in b), so the per-axis min / max pairs of node_hit go away
 // and the results are node_hit's bit for bit.  SlabOff: byte offsets of the
 // near / far plane pairs (left, right) in a BvhNode2.
-#ifndef RT_SIGNED_SLAB
-#define RT_SIGNED_SLAB 1
-#endif
 struct SlabOff { uint32_t nx, ny, nz, fx, fy, fz; };
 __device__ __forceinline__ SlabOff slab_off(const BoxRay& r) {
     SlabOff o;                                              // far = near ^ (lo ^ hi offset)
@@ -1159,8 +1148,8 @@ __device__ __forceinline__ void bvh_closest_lane(const DevScene& sc, const v3 o,
                                                  const int32_t* __restrict__ fid = nullptr) {
     constexpr int32_t kDone = INT32_MIN;
     const double a = dot(d, d), ia = 1.0 / a;
-    // 16-bit stacks: the LDS-tree walks; RT_SIGNED_SLAB 1 = the time-0 tree only, 2 = also the all-times tree
-    constexpr bool SIGNED = sizeof(SE) == 2 && (RT_SIGNED_SLAB == 2 || (RT_SIGNED_SLAB == 1 && FROZEN));
+    // 16-bit stacks: the LDS-tree walks; sign-selected planes for the time-0 tree only
+    constexpr bool SIGNED = sizeof(SE) == 2 && FROZEN;
     static_assert(!(WIDE && SIGNED), "the sign-selected LDS walks serve scenes without curves only");
     using BR = typename std::conditional<WIDE, BoxRayW, BoxRay>::type;
     BR br;
@@ -1180,25 +1169,17 @@ __device__ __forceinline__ void bvh_closest_lane(const DevScene& sc, const v3 o,
     const uint32_t slim = (uint32_t)lmax * stride;
     int32_t node = FROZEN ? sc.fbvh2_root : sc.bvh2_root, pend = kDone;
     float tcap = f32_up(closest);                              // box t range, updated after each leaf
-#ifdef RT_STATS
-    uint32_t n_node = 0, n_leaf = 0, n_sph = 0, n_msph = 0, n_inner = 0, n_outer = 0;
-#endif
+    StatCount n_node{}, n_leaf{}, n_sph{}, n_msph{}, n_inner{}, n_outer{};
     while (node != kDone || pend != kDone) {
-#ifdef RT_STATS
         ++n_outer;
-#endif
         while (node != kDone) {
-#ifdef RT_STATS
             ++n_inner;
-#endif
             if (node < 0) {                                   // a leaf
                 if (pend != kDone) break;                     // one is already parked
                 pend = node;
                 node = sp ? stack_ref(lstk[sp -= stride]) : kDone;
             } else {
-#ifdef RT_STATS
                 ++n_node;
-#endif
                 float tl, tr;
                 bool hl, hr;
                 int2 N;                                       // child refs (l, r)
@@ -1227,36 +1208,26 @@ __device__ __forceinline__ void bvh_closest_lane(const DevScene& sc, const v3 o,
         }
         if (pend != kDone) {
             if constexpr (DIRECT) {
-#ifdef RT_STATS
                 ++n_leaf; ++n_sph;
-#endif
                 const SphereRec S = fsph[~pend];
                 sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, ~pend, closest, fbest);
             } else {
                 const BvhLeaf L = leaves[~pend];
-#ifdef RT_STATS
                 ++n_leaf;
-#endif
                 if (FROZEN) {
                     for (int s = L.sb; s < L.sb + L.sn; ++s) {
-#ifdef RT_STATS
                         ++n_sph;
-#endif
                         const SphereRec S = fsph[s];
                         sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, s, closest, fbest);
                     }
                 } else {
                     for (int s = L.sb; s < L.sb + L.sn; ++s) {
-#ifdef RT_STATS
                         ++n_sph;
-#endif
                         const SphereRec S = sph[s];
                         sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, bs + s, closest, best);
                     }
                     for (int s = L.mb; s < L.mb + L.mn; ++s) {
-#ifdef RT_STATS
                         ++n_msph;
-#endif
                         const MSphereRec S = msph[s];
                         const double frac = sc.msph_shared ? frac_shared : (time - S.t0) / S.den;
                         const v3 cen = mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * frac;
@@ -1269,11 +1240,12 @@ __device__ __forceinline__ void bvh_closest_lane(const DevScene& sc, const v3 o,
         }
     }
     if (FROZEN && fbest >= 0) best = fid[fbest];
-#ifdef RT_STATS
-    constexpr int so = FROZEN ? 16 : 0;
-    RT_STAT(so + 0, 1); RT_STAT(so + 1, n_node); RT_STAT(so + 2, n_leaf); RT_STAT(so + 3, n_sph);
-    RT_STAT(so + 4, n_msph); RT_STAT(so + 5, n_inner); RT_STAT(so + 6, n_outer);
-    {   // wave-level iterations: the wave runs until its slowest lane is done
+    if constexpr (kStats) {
+        constexpr int so = FROZEN ? kStatTree0 : 0;
+        stat_add(so + kStatRays, 1); stat_add(so + kStatNodes, n_node); stat_add(so + kStatLeaves, n_leaf);
+        stat_add(so + kStatSpheres, n_sph); stat_add(so + kStatMSpheres, n_msph);
+        stat_add(so + kStatInner, n_inner); stat_add(so + kStatOuter, n_outer);
+        // wave-level iterations: the wave runs until its slowest lane is done
         const unsigned long long act = __ballot(1);
         uint32_t mi = 0, mo = 0;
         for (int l = 0; l < 64; ++l) {
@@ -1282,10 +1254,10 @@ __device__ __forceinline__ void bvh_closest_lane(const DevScene& sc, const v3 o,
             mo = max(mo, (uint32_t)__builtin_amdgcn_readlane((int)n_outer, l));
         }
         if ((threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)act) - 1)) {
-            RT_STAT(so + 7, 1); RT_STAT(so + 8, mi); RT_STAT(so + 9, mo); RT_STAT(so + 10, __popcll(act));
+            stat_add(so + kStatWaves, 1); stat_add(so + kStatWaveInner, mi); stat_add(so + kStatWaveOuter, mo);
+            stat_add(so + kStatLanes, __popcll(act));
         }
     }
-#endif
 }
 
 // Per-lane traversal of a BVH that holds curves: spheres are tested on the
@@ -1308,21 +1280,15 @@ __device__ __forceinline__ void bvh_closest_curves(const DevScene& sc, const v3 
     bool trav = true;
     int pb = 0, pe = 0;                         // this lane's curves still to queue
     uint32_t qn = 0, svn = 0;                   // queued candidates, survivors awaiting subdivision
-#ifdef RT_STATS
-    uint32_t n_node = 0, n_leaf = 0, n_cand = 0, n_flush = 0, n_iter = 0;
-#endif
+    StatCount n_node{}, n_leaf{}, n_cand{}, n_flush{}, n_iter{};
     // a lane visits each node and leaf at most once and queues each curve at most once, two per step
     const uint32_t cap = 2u * (uint32_t)(sc.n_bvh2 + sc.n_bleaf) + (uint32_t)sc.n_bez + 1024u;
     for (uint32_t it = 0;; ++it) {          // wave-uniform
         if (it > cap) { raise_fault(RT_FAULT_CURVE); break; }
-#ifdef RT_STATS
         ++n_iter;
-#endif
         if (pb >= pe && trav) {                 // lanes with curves pending only queue them below
             if (node >= 0) {
-#ifdef RT_STATS
                 ++n_node;
-#endif
                 const BvhNode2 N = sc.bvh2[node];
                 const float tcap = f32_up(closest * tscale);
                 float tl, tr;
@@ -1344,9 +1310,7 @@ __device__ __forceinline__ void bvh_closest_curves(const DevScene& sc, const v3 
                 }
             } else if (~node >= kDirectCurve) {               // a leaf holding one curve
                 pb = ~node - kDirectCurve; pe = pb + 1;
-#ifdef RT_STATS
                 ++n_leaf; ++n_cand;
-#endif
                 if (sp == 0) {
                     trav = false;
                 } else {
@@ -1366,9 +1330,7 @@ __device__ __forceinline__ void bvh_closest_curves(const DevScene& sc, const v3 
                     sphere_test(o, d, a, ia, cen, S.rr, bm + s, closest, best);
                 }
                 pb = L.bb; pe = L.bb + L.bn;
-#ifdef RT_STATS
                 ++n_leaf; n_cand += (uint32_t)L.bn;
-#endif
                 if (sp == 0) {
                     trav = false;
                 } else {
@@ -1386,9 +1348,7 @@ __device__ __forceinline__ void bvh_closest_curves(const DevScene& sc, const v3 
         }
         const bool more = __ballot(trav || pb < pe) != 0ull;
         if (qn >= 64u || (!more && (qn > 0u || svn > 0u))) {
-#ifdef RT_STATS
             ++n_flush;
-#endif
             W.cl[lane] = closest;
             wave_sync();
             svn = bez_stage_a(sc, W, qn, svn);
@@ -1407,12 +1367,14 @@ __device__ __forceinline__ void bvh_closest_curves(const DevScene& sc, const v3 
         }
         if (!more) break;
     }
-#ifdef RT_STATS
-    RT_STAT(11, 1); RT_STAT(12, n_node); RT_STAT(13, n_leaf); RT_STAT(14, n_cand);
-    if (lane == (uint32_t)__ffsll((long long)__ballot(1)) - 1u) {
-        RT_STAT(27, n_flush); RT_STAT(28, n_iter); RT_STAT(29, 1); RT_STAT(30, __popcll(__ballot(1)));
+    if constexpr (kStats) {
+        stat_add(kStatCurveRays, 1); stat_add(kStatCurveNodes, n_node); stat_add(kStatCurveLeaves, n_leaf);
+        stat_add(kStatCurveCands, n_cand);
+        if (lane == (uint32_t)__ffsll((long long)__ballot(1)) - 1u) {
+            stat_add(kStatCurveFlushes, n_flush); stat_add(kStatCurveIters, n_iter); stat_add(kStatCurveWaves, 1);
+            stat_add(kStatCurveLanes, __popcll(__ballot(1)));
+        }
     }
-#endif
 }
 
 // ---------------------------------------------------------- closest hit
@@ -1975,11 +1937,8 @@ __device__ __forceinline__ uint32_t wave_append(const int cls, const uint32_t sh
 // bvh_closest_curves; a ray finishes once its traversal has ended and every
 // curve candidate it queued has been resolved by a batch (W.done).
 // =====================================================================
-static_assert(4 * sizeof(BezWave) + 256 * sizeof(uint32_t) * RT_CURVE_LDS_STACK <= 160 * 1024 / RT_CURVE_WAVES,
-              "k_extend_curves: RT_CURVE_WAVES blocks of BezWave state and LDS stack columns must fit a CU's LDS");
-#ifndef RT_CURVE_PREFETCH
-#define RT_CURVE_PREFETCH 1            // load the lane's next BVH4 node one iteration ahead (32 VGPRs)
-#endif
+static_assert(4 * sizeof(BezWave) + 256 * sizeof(uint32_t) * kCurveLdsStack <= 160 * 1024 / kCurveWaves,
+              "k_extend_curves: kCurveWaves blocks of BezWave state and LDS stack columns must fit a CU's LDS");
 // FUSE (1: device libm, 2: the exact libm): every depth from fz.depth on in one launch, so the launch
 // drains once per chunk instead of once per depth (C5: ~1.1 ms per depth launch).  A lane whose ray is
 // resolved parks its hit in the wave's hand-off ring (FuseHit) and takes the next ray at once; when 64
@@ -1993,7 +1952,7 @@ template <bool EX>
 __device__ __forceinline__ bool fused_shade(const DevScene& sc, const RenderParams& rp, PathRegs& p, const double t,
                                             const int32_t leaf, v3& L);   // below shade_hit
 template <int FUSE = 0>
-__global__ __launch_bounds__(256, RT_CURVE_WAVES) void k_extend_curves(const DevScene sc, const RenderParams rp,
+__global__ __launch_bounds__(256, kCurveWaves) void k_extend_curves(const DevScene sc, const RenderParams rp,
                                                        const PathState st, const QView in, uint32_t n, HitBuf hit,
                                                        uint32_t shard_cap, uint32_t* __restrict__ counts,
                                                        const bool depth0, unsigned int* __restrict__ claim,
@@ -2013,16 +1972,14 @@ __global__ __launch_bounds__(256, RT_CURVE_WAVES) void k_extend_curves(const Dev
     uint32_t dep = FUSE ? fz.depth : 0u, fsegs = 0;  // FUSE: the lane's path depth, continuation segments
     // The ray itself (o, d, time) is not kept in registers across iterations: the BVH step needs only
     // its box-test form and t scale, the sphere leaves and the finish reload it (ray_of below), so stage
-    // B's walk state fits beside the loop's (registers cap the waves per SIMD, RT_CURVE_WAVES)
+    // B's walk state fits beside the loop's (registers cap the waves per SIMD, kCurveWaves)
     double tscale = 1.0, closest = kTmax;
     int32_t best = -1, node = 0;
     // best's material class (leaf_cls), loaded whenever best changes: the load is in flight while the
     // traversal goes on, not a round trip of the finish
     int32_t bcls = -1;
     BoxRayW br{};                                   // rays from anywhere (BoxRayW)
-#if RT_CURVE_PREFETCH
-    BvhNode4 N{};                                   // the lane's next node, loaded one iteration ahead
-#endif
+    BvhNode4 N{};                                   // the lane's next node, loaded one iteration ahead (32 VGPRs)
     auto ray_of = [&](v3& o, v3& d, double& tm) {
         const RayRec R = st.ray[i];
         o = mk(R.ox, R.oy, R.oz);
@@ -2057,9 +2014,7 @@ __global__ __launch_bounds__(256, RT_CURVE_WAVES) void k_extend_curves(const Dev
         tscale = fmax(1.0, 1.0 / sqrt(dot(d, d)));
         bez_ray(o, d, W.ray[lane]);
         sp = 0; node = sc.bvh4_root; trav = gb < sc.n_groups;
-#if RT_CURVE_PREFETCH
         if (trav && node >= 0) N = sc.bvh4[node];
-#endif
     };
     uint32_t qn = 0, svn = 0;                       // wave-uniform: queued candidates, survivors
     // the wave's survivor ring (launch_extend_curves keeps the grid within sc.ring_waves) and the ring
@@ -2079,37 +2034,34 @@ __global__ __launch_bounds__(256, RT_CURVE_WAVES) void k_extend_curves(const Dev
     // a lane whose ray hit the cap stays out of the refill for good: candidates it queued may still sit
     // in W.q / W.sv, and a new ray in the lane would take their results (W.done, hz / hkey)
     bool dead = false;
-#ifdef RT_STATS
-    uint32_t st_iter = 0, st_steps = 0, st_busy = 0, st_wait = 0, st_flush = 0;
-    const unsigned long long st_clk0 = __builtin_amdgcn_s_memtime();
-    unsigned long long st_clk_a = 0, st_clk1 = 0, st_clk2 = 0, st_clk3 = 0, st_t = 0;
-#endif
+    StatCount st_iter{}, st_steps{}, st_busy{}, st_wait{}, st_flush{};
+    StatClock st_clk_a{}, st_clk1{}, st_clk2{}, st_clk3{};      // stage A, steps 1 - 3
+    const unsigned long long st_clk0 = stat_clock();
+    unsigned long long st_t = 0;
     for (;;) {
         // only iterations in which the lane itself works count: one waiting for a batch
         // other lanes trigger is bounded by their work (the last batch runs once no lane can add)
         if (active && (trav || pb < pe) && ++ray_it > ray_cap) {
             raise_fault(RT_FAULT_PATH); active = false; trav = false; pb = pe; dead = true;
         }
-#ifdef RT_STATS
-        ++st_iter;
-        if (active && trav && pb >= pe) ++st_steps;
-        if (active) ++st_busy;
-        if (active && !trav && pb >= pe) ++st_wait;
-#endif
-#ifdef RT_STATS
-        st_t = __builtin_amdgcn_s_memtime();
-#endif
+        if constexpr (kStats) {
+            ++st_iter;
+            if (active && trav && pb >= pe) ++st_steps;
+            if (active) ++st_busy;
+            if (active && !trav && pb >= pe) ++st_wait;
+            st_t = stat_clock();
+        }
         // 1. rays whose traversal ended and whose curves are all resolved: the
         //    groups after the BVH, then miss (sky) or hit + material queue
         int cls = -1;
         HitRec hr{};
-        // Finished lanes are written out (and refilled in step 2) together, once RT_CURVE_FINISH_BATCH of
+        // Finished lanes are written out (and refilled in step 2) together, once kCurveFinishBatch of
         // them are ready, every active lane is, or the ray list is exhausted: a miss's path-record gather,
         // the queue append's returning atomics and the refill's claim and ray loads are dependent
         // round trips, which cost the wave the same whether one lane or sixteen take them.
         const bool fin = active && !trav && pb >= pe && W.done[lane] == queued;
         const unsigned long long fin_m = __ballot(fin);
-        const bool flush = fin_m != 0ull && (exhausted || __popcll(fin_m) >= RT_CURVE_FINISH_BATCH ||
+        const bool flush = fin_m != 0ull && (exhausted || __popcll(fin_m) >= kCurveFinishBatch ||
                                              fin_m == __ballot(active));
         if constexpr (FUSE != 0) {
             // park every resolved ray at once (its lane takes the next one in step 2)
@@ -2125,7 +2077,7 @@ __global__ __launch_bounds__(256, RT_CURVE_WAVES) void k_extend_curves(const Dev
             bool round = npk >= 64u;  // a whole wave (48 / 32: -0.1 / -1.1 % at 1 spp, -0.9 / -2.9 % at 8)
             if (!round && npk > 0u && exhausted && rd_head == rd_tail) {
                 const unsigned long long am = __ballot(active);
-                round = am == 0ull || __popcll(__ballot(!active && !dead)) >= RT_CURVE_FINISH_BATCH;
+                round = am == 0ull || __popcll(__ballot(!active && !dead)) >= kCurveFinishBatch;
             }
             if (round) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // the parked hits other lanes wrote
@@ -2199,9 +2151,7 @@ __global__ __launch_bounds__(256, RT_CURVE_WAVES) void k_extend_curves(const Dev
                                                     counts, shard_cap);
             if (cls >= 0 && slot != kNoSlot) hit.h[(size_t)cls * hit.stride + slot] = hr;
         }
-#ifdef RT_STATS
-        { const unsigned long long t = __builtin_amdgcn_s_memtime(); st_clk1 += t - st_t; st_t = t; }
-#endif
+        if constexpr (kStats) { const unsigned long long t = stat_clock(); st_clk1 += t - st_t; st_t = t; }
         // 2. free lanes take the next rays: FUSE, the wave's ready paths first; then claimed positions in the
         //    input queue
         unsigned long long need = __ballot(!active && !dead);
@@ -2253,16 +2203,11 @@ __global__ __launch_bounds__(256, RT_CURVE_WAVES) void k_extend_curves(const Dev
             // FUSE: done once nothing is parked or ready (or no lane is left to take a path: a fault)
             if ((exhausted && pk_head == pk_tail && rd_head == rd_tail) || __ballot(!dead) == 0ull) break;
         }
-#ifdef RT_STATS
-        { const unsigned long long t = __builtin_amdgcn_s_memtime(); st_clk2 += t - st_t; st_t = t; }
-#endif
+        if constexpr (kStats) { const unsigned long long t = stat_clock(); st_clk2 += t - st_t; st_t = t; }
         // 3. one BVH4 step (bvh_closest_curves over the collapsed tree): the node's hit children
         //    nearest first, the nearest entered, the others pushed
         if (active && trav && pb >= pe) {
             if (node >= 0) {
-#if !RT_CURVE_PREFETCH
-                const BvhNode4 N = sc.bvh4[node];
-#endif
                 const float tcap = f32_up(closest * tscale);
                 float key[4];
                 int32_t ref[4];
@@ -2338,13 +2283,9 @@ __global__ __launch_bounds__(256, RT_CURVE_WAVES) void k_extend_curves(const Dev
                 else node = pop();
             }
         }
-#if RT_CURVE_PREFETCH
         // the next node's record, in flight while the batches below run (+5 % at C5 with 2 waves per SIMD)
         if (active && trav && node >= 0) N = sc.bvh4[node];
-#endif
-#ifdef RT_STATS
-        { const unsigned long long t = __builtin_amdgcn_s_memtime(); st_clk3 += t - st_t; st_t = t; }
-#endif
+        if constexpr (kStats) { const unsigned long long t = stat_clock(); st_clk3 += t - st_t; st_t = t; }
         // 4. queue one of the lane's curve candidates (kBezQ: at most one per lane per step; a leaf with
         //    several curves queues them over the next iterations, its traversal paused meanwhile)
         {
@@ -2356,26 +2297,15 @@ __global__ __launch_bounds__(256, RT_CURVE_WAVES) void k_extend_curves(const Dev
         // 5. batches: root culls at 64 queued candidates, subdivisions in
         //    multiples of 64 (everything once no lane can add candidates)
         const bool more = __ballot(active && (trav || pb < pe)) != 0ull;
-#if RT_BEZ_WAIT_FLUSH
-        const bool press = __popcll(__ballot(active && !trav && pb >= pe && W.done[lane] != queued)) >= RT_BEZ_WAIT_FLUSH;
-#else
-        constexpr bool press = false;
-#endif
-        if (qn >= (uint32_t)RT_BEZ_QFLUSH || ((!more || press) && (qn > 0u || svn > 0u))) {
-#ifdef RT_STATS
-            ++st_flush;
-#endif
+        if (qn >= (uint32_t)kBezQFlush || (!more && (qn > 0u || svn > 0u))) {
+            if constexpr (kStats) ++st_flush;
             W.cl[lane] = closest;
             wave_sync();
-#ifdef RT_STATS
-            const unsigned long long ca = __builtin_amdgcn_s_memtime();
-#endif
+            const unsigned long long ca = stat_clock();
             svn = bez_stage_a<true>(sc, W, qn, svn, ring, rtail);
-#ifdef RT_STATS
-            st_clk_a += __builtin_amdgcn_s_memtime() - ca;
-#endif
+            if constexpr (kStats) st_clk_a += stat_clock() - ca;
             qn = 0;
-            const uint32_t nb = (more && !press) ? (svn >= (uint32_t)RT_BEZ_HOLD ? svn - svn % 64u : 0u) : svn;
+            const uint32_t nb = more ? (svn >= (uint32_t)kBezHold ? svn - svn % 64u : 0u) : svn;
             if (nb > 0u) {
                 W.hz[lane] = INFINITY;
                 W.hkey[lane] = 0ull;
@@ -2398,30 +2328,23 @@ __global__ __launch_bounds__(256, RT_CURVE_WAVES) void k_extend_curves(const Dev
         for (int off = 32; off > 0; off >>= 1) fsegs += __shfl_xor(fsegs, off, 64);
         if (lane == 0u && fsegs) atomicAdd(fz.segs, (unsigned long long)fsegs);
     }
-#ifdef RT_STATS
-    RT_STAT(20, st_steps); RT_STAT(21, st_busy); RT_STAT(22, st_wait);
-    if (lane == 0u) {
-        RT_STAT(23, st_iter); RT_STAT(24, 1); RT_STAT(25, st_flush);
-        RT_STAT(40, __builtin_amdgcn_s_memtime() - st_clk0); RT_STAT(41, st_clk_a);
-        RT_STAT(42, st_clk1); RT_STAT(43, st_clk2); RT_STAT(44, st_clk3);   // kernel / stage A clocks per wave
+    if constexpr (kStats) {
+        stat_add(kStatKcSteps, st_steps); stat_add(kStatKcBusy, st_busy); stat_add(kStatKcWait, st_wait);
+        if (lane == 0u) {
+            stat_add(kStatKcIters, st_iter); stat_add(kStatKcWaves, 1); stat_add(kStatKcFlushes, st_flush);
+            stat_add(kStatKcClock, stat_clock() - st_clk0); stat_add(kStatKcClockA, st_clk_a);
+            stat_add(kStatKcClock1, st_clk1); stat_add(kStatKcClock2, st_clk2); stat_add(kStatKcClock3, st_clk3);
+        }
     }
-#endif
 }
 
-#ifndef RT_EXTLDS_BLOCK
-#define RT_EXTLDS_BLOCK 512
-#endif
+constexpr int kExtLdsBlock = 512;      // threads per block of the LDS kernels
 // Waves per SIMD the LDS kernels are compiled for (VGPR cap 512 / waves).
 // k_extend_lds at 8 (64 VGPRs, spilling per-ray state outside the node loop)
 // measured +5 % on the overlapped two-lane frame against 6 (80 VGPRs), -1 %
 // with one lane; k_camera stays at 6 (8 made no difference and spills more).
-#ifndef RT_EXTLDS_WAVES
-#define RT_EXTLDS_WAVES 8
-#endif
-#ifndef RT_CAMERA_WAVES
-#define RT_CAMERA_WAVES 6
-#endif
-constexpr int kExtLdsBlock = RT_EXTLDS_BLOCK;
+constexpr int kExtLdsWaves = 8;
+constexpr int kCameraWaves = 6;
 // Copy n records of T from HBM into LDS, 16-B words, all threads of the block.
 template <class T>
 __device__ __forceinline__ void stage_lds(T* dst, const T* src, const int n, const int nthreads) {
@@ -2458,13 +2381,13 @@ __host__ __device__ __forceinline__ int tree0_lds_leaves(const DevScene& sc) { r
 __host__ __device__ __forceinline__ size_t extend_lds_need(const DevScene& sc) {
     return (size_t)sc.n_fbvh2 * sizeof(BvhNode2) + (size_t)tree0_lds_leaves(sc) * sizeof(BvhLeaf) +
            (size_t)sc.n_fsph * sizeof(SphereRec) +
-           (size_t)RT_EXTLDS_BLOCK * (size_t)(sc.lane_stack > 0 ? sc.lane_stack : 1) * sizeof(uint16_t) +
+           (size_t)kExtLdsBlock * (size_t)(sc.lane_stack > 0 ? sc.lane_stack : 1) * sizeof(uint16_t) +
            lds_tail_bytes(sc);
 }
 __host__ __device__ __forceinline__ size_t camera_lds_need(const DevScene& sc) {     // all-times tree
     return (size_t)sc.n_bvh2 * sizeof(BvhNode2) + (size_t)sc.n_bleaf * sizeof(BvhLeaf) +
            (size_t)sc.n_sph * sizeof(SphereRec) + (size_t)sc.n_msph * sizeof(MSphereRec) +
-           (size_t)RT_EXTLDS_BLOCK * (size_t)(sc.lane_stack > 0 ? sc.lane_stack : 1) * sizeof(uint16_t) +
+           (size_t)kExtLdsBlock * (size_t)(sc.lane_stack > 0 ? sc.lane_stack : 1) * sizeof(uint16_t) +
            lds_tail_bytes(sc);
 }
 // stage n 32-bit words (fid, packed class bytes)
@@ -2481,7 +2404,7 @@ __device__ __forceinline__ void stage_words(uint32_t* dst, const uint32_t* src, 
 // =====================================================================
 
 template <bool SOLO>
-__global__ __launch_bounds__(kExtLdsBlock, RT_EXTLDS_WAVES) void k_extend_lds(const DevScene sc, const RenderParams rp,
+__global__ __launch_bounds__(kExtLdsBlock, kExtLdsWaves) void k_extend_lds(const DevScene sc, const RenderParams rp,
                                                              const PathState st, const QView in, uint32_t n,
                                                              HitBuf hit, uint32_t shard_cap,
                                                              uint32_t* __restrict__ counts, const uint32_t lds_bytes,
@@ -2543,7 +2466,7 @@ __global__ __launch_bounds__(kExtLdsBlock, RT_EXTLDS_WAVES) void k_extend_lds(co
 // something store their depth-0 state for the shade kernels.
 // =====================================================================
 template <bool ALL, bool SOLO>
-__global__ __launch_bounds__(kExtLdsBlock, RT_CAMERA_WAVES) void k_camera(const DevScene sc, const RenderParams rp,
+__global__ __launch_bounds__(kExtLdsBlock, kCameraWaves) void k_camera(const DevScene sc, const RenderParams rp,
                                                                           const PathState st, const uint32_t n,
                                                                           HitBuf hit, uint32_t shard_cap,
                                                                           uint32_t* __restrict__ counts,
@@ -2615,7 +2538,7 @@ __global__ __launch_bounds__(kExtLdsBlock, RT_CAMERA_WAVES) void k_camera(const 
 // shares with those kernels, and not next to k_hit_rays.
 // =====================================================================
 template <bool TIME0, bool ALL, bool SOLO>
-__global__ __launch_bounds__(kExtLdsBlock, TIME0 ? RT_EXTLDS_WAVES : RT_CAMERA_WAVES)
+__global__ __launch_bounds__(kExtLdsBlock, TIME0 ? kExtLdsWaves : kCameraWaves)
 void k_hit_rays_lds(const DevScene sc, const double* __restrict__ rays, const uint32_t n, double* __restrict__ out_t,
                     int32_t* __restrict__ out_mat, const uint32_t lds_bytes) {
     static_assert(!(TIME0 && ALL), "k_extend_lds stages the time-0 tree only");
@@ -2773,9 +2696,6 @@ __device__ __forceinline__ v3 image_texel(const DevScene& sc, const DevTexture& 
 // TL: the texture level a kernel is compiled for.  kTexPlain compiles the noise / marble cases out (scenes
 // without them); kTexImage adds image textures (and the hit record's u, v) to kTexPerlin
 constexpr int kTexPlain = 0, kTexPerlin = 1, kTexImage = 2;
-static int scene_tex_level(const DevScene& sc) {     // the instances a scene's launches take
-    return sc.has_image_tex ? kTexImage : sc.has_noise_tex ? kTexPerlin : kTexPlain;
-}
 template <int TL>
 __device__ __forceinline__ v3 tex_value(const DevScene& sc, const PerlinLds& P, int id, v3 p, const double u, const double v) {   // texture.scm
     for (int guard = 0; guard < 64; ++guard) {
@@ -3082,19 +3002,12 @@ __device__ __forceinline__ void stage_perlin(const DevScene& sc, PerlinLds& P) {
 // not kept: its occupancy is the lambertian code's, and the memory-bound
 // metal / dielectric hits lost more than the shared lines saved — DESIGN §4.)
 // =====================================================================
-#ifndef RT_SHADE_WAVES
-#define RT_SHADE_WAVES 1               // lambertian / light: the compiler's choice (127 VGPRs, 4 waves)
-#endif
-#ifndef RT_SHADE_WAVES_MD
-#define RT_SHADE_WAVES_MD 1            // metal / dielectric (memory-bound gathers)
-#endif
-// the exact libm's lambertian kernels without Perlin tables or the light mixture (EX) at 4 waves: with the
-// bounce angles' in-range sin / cos (rt_cos_sin) they need 137 VGPRs left alone and fit 128 with no spill
+// Waves per SIMD: 1 = the compiler's choice (lambertian / light: 127 VGPRs, 4 waves; metal / dielectric:
+// memory-bound gathers), except the exact libm's lambertian kernels without Perlin tables or the light
+// mixture (EX) at 4 waves: with the bounce angles' in-range sin / cos (rt_cos_sin) they need 137 VGPRs left
+// alone and fit 128 with no spill
 template <int MAT, int TL, bool LS, bool EX>
-constexpr int shade_waves() {
-    return (MAT == MAT_METAL || MAT == MAT_DIELECTRIC) ? RT_SHADE_WAVES_MD
-         : (MAT == MAT_LAMBERTIAN && EX && TL == kTexPlain && !LS) ? 4 : RT_SHADE_WAVES;
-}
+constexpr int shade_waves() { return (MAT == MAT_LAMBERTIAN && EX && TL == kTexPlain && !LS) ? 4 : 1; }
 template <int MAT, int TL, bool LS, bool LL, bool EX>
 __global__ __launch_bounds__(256, (shade_waves<MAT, TL, LS, EX>())) void k_shade(const DevScene* __restrict__ scp, const RenderParams rp,
                                                                 const PathState in, const HitRec* __restrict__ hq,
@@ -3143,11 +3056,10 @@ __global__ __launch_bounds__(256, (shade_waves<MAT, TL, LS, EX>())) void k_shade
 // depth 100): one thread per remaining path runs extend + shade in a loop
 // instead of ~100 more wavefront launches with a host sync each.
 // =====================================================================
-#ifndef RT_FINISH_WAVES
-#define RT_FINISH_WAVES 4             // plain-sphere tails without Perlin / light mixture: 128 VGPRs, 4 waves per SIMD
-#endif                                // (the compiler's choice is 143: 3 waves; the other variants would spill at 128)
+// plain-sphere tails without Perlin / light mixture: 128 VGPRs, 4 waves per SIMD (the compiler's choice is
+// 143: 3 waves; the other variants would spill at 128)
 template <int F, int TL, bool LSM>
-constexpr int finish_waves() { return (F == 0 && TL == kTexPlain && !LSM) ? RT_FINISH_WAVES : 1; }
+constexpr int finish_waves() { return (F == 0 && TL == kTexPlain && !LSM) ? 4 : 1; }
 template <int F, int TL, bool LSM, bool SOLO = false, bool EX = false>
 __global__ __launch_bounds__(256, (finish_waves<F, TL, LSM>())) void k_finish(const DevScene* __restrict__ scp, const RenderParams rp, const PathState st,
                                                 const QView in, uint32_t n,
@@ -3331,7 +3243,7 @@ __global__ __launch_bounds__(256) void k_features(const DevScene sc, const Rende
 }
 
 // ------------------------------------------------------------ launchers
-#define HIP_RETURN_IF(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
+// (errors pass up as `if (const hipError_t e = call) return e;`: hipSuccess is 0)
 hipError_t launch_raygen(const DevScene& sc, const RenderParams& rp, const PathState& st,
                          hipStream_t s) {
     const uint32_t blocks = (rp.B + 255u) / 256u;
@@ -3346,114 +3258,177 @@ static bool finish_generic() {               // RTAMD_FINISH_GENERIC: the group-
 static int scene_features(const DevScene& sc) {
     return (sc.n_bez > 0 ? kFeatCurves : 0) | (sc.n_med > 0 || sc.n_klein > 0 ? kFeatExtra : 0);
 }
+static int scene_tex_level(const DevScene& sc) {     // the instances a scene's launches take
+    return sc.has_image_tex ? kTexImage : sc.has_noise_tex ? kTexPerlin : kTexPlain;
+}
 static uint32_t curve_blocks() {            // cap on the persistent curve grid (RTAMD_CURVE_BLOCKS; 0 = per-ray k_extend)
     const char* e = std::getenv("RTAMD_CURVE_BLOCKS");  // read per launch: tests switch it inside one process
     return e ? (uint32_t)std::strtoul(e, nullptr, 10) : 1u << 20;
 }
 bool curve_persistent() { return curve_blocks() > 0u; }   // the host's check before a fused launch
-// resident blocks of a curve kernel instance for its dynamic LDS, cached per (kernel, device, LDS bytes)
-static hipError_t curve_occupancy(const void* f, const size_t lds, uint32_t* out) {
-    static const void* occ_f[3] = {nullptr, nullptr, nullptr};
-    static int occ_dev[3] = {-1, -1, -1};
-    static size_t occ_lds[3] = {~(size_t)0, ~(size_t)0, ~(size_t)0};
-    static uint32_t occ_blocks[3] = {0, 0, 0};
-    int dev = 0;
-    HIP_RETURN_IF(hipGetDevice(&dev));
-    const int slot = f == reinterpret_cast<const void*>(&k_extend_curves<1>) ? 1
-                   : f == reinterpret_cast<const void*>(&k_extend_curves<2>) ? 2 : 0;
-    if (occ_f[slot] != f || occ_lds[slot] != lds || occ_dev[slot] != dev) {
-        int per_cu = 0, cus = 0;
-        HIP_RETURN_IF(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, 256, lds));
-        HIP_RETURN_IF(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        occ_blocks[slot] = (uint32_t)(per_cu > 0 ? per_cu : 1) * (uint32_t)(cus > 0 ? cus : 1);
-        occ_lds[slot] = lds;
-        occ_dev[slot] = dev;
-        occ_f[slot] = f;
+// the per-lane BVH stack columns of a 256-thread block in dynamic LDS
+static size_t lane_stack_lds(const DevScene& sc, const size_t entry = sizeof(uint32_t)) {
+    return (size_t)256 * (size_t)(sc.lane_stack > 0 ? sc.lane_stack : 1) * entry;
+}
+// every shard gets the same number of blocks
+static uint32_t shard_blocks(const uint32_t blocks) { return (blocks + kShards - 1) / kShards * kShards; }
+
+// Kernel selection.  Every instance of a kernel template has one signature, so a family's selector maps the
+// run-time facts to a typed pointer, and that pointer is what the launch, hipFuncSetAttribute, the occupancy
+// query and its cache key all use.  Only the instances a selector names are compiled.
+// dispatch(f, a, b, ...): f(A, B, ...) with each run-time bool or UpTo as a std::integral_constant
+template <int N> struct UpTo { int v; };     // an int in 0 .. N for dispatch (anything above counts as N)
+template <class Fn> static auto dispatch(Fn&& f) { return f(); }
+template <class Fn, int N, class... Rest> static auto dispatch(Fn&& f, UpTo<N> v, Rest... rest);
+template <class Fn, class... Rest>
+static auto dispatch(Fn&& f, bool b, Rest... rest) {
+    return b ? dispatch([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+             : dispatch([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+template <class Fn, int N, class... Rest>
+static auto dispatch(Fn&& f, UpTo<N> v, Rest... rest) {
+    if constexpr (N > 0) if (v.v < N) return dispatch(f, UpTo<N - 1>{v.v}, rest...);
+    return dispatch([&](auto... c) { return f(std::integral_constant<int, N>{}, c...); }, rest...);
+}
+using TexLevel = UpTo<kTexImage>;
+using ExtendKernel = void (*)(DevScene, RenderParams, PathState, QView, uint32_t, HitBuf, uint32_t, uint32_t*, bool);
+using CurveKernel = void (*)(DevScene, RenderParams, PathState, QView, uint32_t, HitBuf, uint32_t, uint32_t*, bool,
+                             unsigned int*, CurveFuse);
+using ExtendLdsKernel = void (*)(DevScene, RenderParams, PathState, QView, uint32_t, HitBuf, uint32_t, uint32_t*,
+                                 uint32_t, unsigned long long*);
+using CameraKernel = void (*)(DevScene, RenderParams, PathState, uint32_t, HitBuf, uint32_t, uint32_t*, uint32_t,
+                              unsigned long long*);
+using HitRaysKernel = void (*)(DevScene, const double*, uint32_t, double*, int32_t*);
+using HitRaysLdsKernel = void (*)(DevScene, const double*, uint32_t, double*, int32_t*, uint32_t);
+using ShadeKernel = void (*)(const DevScene*, RenderParams, PathState, const HitRec*, QView, PathState, uint32_t*,
+                             uint32_t, uint32_t);
+using FinishKernel = void (*)(const DevScene*, RenderParams, PathState, QView, uint32_t, unsigned long long*, int,
+                              uint32_t);
+using FeaturesKernel = void (*)(DevScene, RenderParams, uint32_t, double*);
+static ExtendKernel extend_kernel(const DevScene& sc) {
+    return dispatch([](auto F) -> ExtendKernel { return k_extend<F()>; }, UpTo<3>{scene_features(sc)});
+}
+// FUSE: 0 one depth, 1 every depth from fuse->depth on with the device libm, 2 with the exact libm
+static CurveKernel curve_kernel(const RenderParams& rp, const CurveFuse* fuse) {
+    return dispatch([](auto FUSE) -> CurveKernel { return k_extend_curves<FUSE()>; }, UpTo<2>{!fuse ? 0 : rp.exact_libm ? 2 : 1});
+}
+// SOLO: the world is one BVH group
+static ExtendLdsKernel extend_lds_kernel(const DevScene& sc) {
+    return sc.bvh_solo ? k_extend_lds<true> : k_extend_lds<false>;
+}
+// ALL: the all-times tree (the scene has moving spheres)
+static CameraKernel camera_kernel(const DevScene& sc) {
+    return dispatch([](auto ALL, auto SOLO) -> CameraKernel { return k_camera<ALL(), SOLO()>; },
+                  !sc.tree0_any_time, sc.bvh_solo != 0);
+}
+static HitRaysKernel hit_rays_kernel(const DevScene& sc) {
+    return scene_features(sc) ? k_hit_rays<kFeatCurves | kFeatExtra> : k_hit_rays<0>;
+}
+// the probe of k_extend_lds's walk (time0) or k_camera's: the instance with that kernel's arguments
+static HitRaysLdsKernel hit_rays_lds_kernel(const DevScene& sc, const bool time0) {
+    if (time0) return sc.bvh_solo ? k_hit_rays_lds<true, false, true> : k_hit_rays_lds<true, false, false>;
+    return dispatch([](auto ALL, auto SOLO) -> HitRaysLdsKernel { return k_hit_rays_lds<false, ALL(), SOLO()>; },
+                  !sc.tree0_any_time, sc.bvh_solo != 0);
+}
+// LS: the light mixture, LL: the leaf records staged in LDS, EX: libm's own sin / cos for the bounce directions
+// (bounce_cos_sin: RT_OPT_EXACT_LIBM, by default in scenes with curves).  Only lambertian scatter uses the
+// light mixture and draws directions; the dielectric attenuation is constant 1, so it has no texture levels
+static ShadeKernel shade_kernel(const int mat, const DevScene& sc, const RenderParams& rp, const bool ll) {
+    const TexLevel tl{scene_tex_level(sc)};
+    switch (mat) {
+    case MAT_LAMBERTIAN:
+        return dispatch([](auto TL, auto LS, auto LL, auto EX) -> ShadeKernel { return k_shade<MAT_LAMBERTIAN, TL(), LS(), LL(), EX()>; },
+                      tl, sc.light.type != LIGHT_OFF, ll, rp.exact_libm != 0);
+    case MAT_METAL:
+        return dispatch([](auto TL, auto LL) -> ShadeKernel { return k_shade<MAT_METAL, TL(), false, LL(), false>; }, tl, ll);
+    case MAT_DIELECTRIC:
+        return ll ? k_shade<MAT_DIELECTRIC, kTexPlain, false, true, false> : k_shade<MAT_DIELECTRIC, kTexPlain, false, false, false>;
+    default:
+        return dispatch([](auto TL, auto LL) -> ShadeKernel { return k_shade<MAT_DIFFUSE_LIGHT, TL(), false, LL(), false>; }, tl, ll);
     }
-    *out = occ_blocks[slot];
+}
+// the texture level of the tail's instance: scenes with curves, media or Kleinian sets carry every material's
+// code, Perlin tables and light mixture included.  The plain-sphere feature set also gets Perlin /
+// light-mixture specialisations: the tail kernel carries every material's code, so dropping the unused
+// ones trims its register file
+static int finish_tex_level(const DevScene& sc) {
+    const int tl = scene_tex_level(sc);
+    return scene_features(sc) > 0 && tl < kTexPerlin ? kTexPerlin : tl;
+}
+static FinishKernel finish_kernel(const DevScene& sc, const RenderParams& rp, const bool solo) {
+    const int f = scene_features(sc), tl = finish_tex_level(sc);
+    const bool ex = rp.exact_libm != 0;
+    if (f > 0)
+        return dispatch([](auto F1, auto IMG, auto EX) -> FinishKernel {
+            return k_finish<F1() + 1, IMG() ? kTexImage : kTexPerlin, true, false, EX()>;
+        }, UpTo<2>{f - 1}, tl == kTexImage, ex);
+    return dispatch([](auto TL, auto LS, auto SOLO, auto EX) -> FinishKernel { return k_finish<0, TL(), LS(), SOLO(), EX()>; },
+                  TexLevel{tl}, sc.light.type != LIGHT_OFF, solo, ex);
+}
+static FeaturesKernel features_kernel(const DevScene& sc) {
+    return dispatch([](auto F, auto TL) -> FeaturesKernel { return k_features<F(), TL()>; },
+                  UpTo<3>{scene_features(sc)}, TexLevel{scene_tex_level(sc)});
+}
+
+// resident blocks of a curve kernel instance for its dynamic LDS, cached per (kernel, device, LDS bytes)
+static hipError_t curve_occupancy(const CurveKernel k, const size_t lds, uint32_t* out) {
+    struct Entry { CurveKernel k; int dev; size_t lds; uint32_t blocks; };
+    static Entry cache[3];                      // one per instance, in the order they are first asked for
+    int dev = 0;
+    if (const hipError_t e = hipGetDevice(&dev)) return e;
+    Entry* e = cache;
+    while (e < cache + 2 && e->k && e->k != k) ++e;
+    if (e->k != k || e->lds != lds || e->dev != dev) {
+        int per_cu = 0, cus = 0;
+        if (const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k), 256, lds)) return e;
+        if (const hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) return e;
+        *e = Entry{k, dev, lds, (uint32_t)(per_cu > 0 ? per_cu : 1) * (uint32_t)(cus > 0 ? cus : 1)};
+    }
+    *out = e->blocks;
     return hipSuccess;
 }
 hipError_t launch_extend(const DevScene& sc, const DevScene*, const RenderParams& rp, const PathState& st, const QView& in,
                          uint32_t n, const HitBuf& hit, uint32_t shard_cap,
                          uint32_t* counts, bool depth0, unsigned int* claim, const CurveFuse* fuse, hipStream_t s) {
     const uint32_t blocks = (n + 255u) / 256u;
-    const size_t lds = (size_t)256 * (size_t)(sc.lane_stack > 0 ? sc.lane_stack : 1) * sizeof(uint32_t);
     // the persistent curve kernel: every curve in the world BVH (its groups outside the BVH are spheres and
     // rects only: group_closest<0>, so the per-lane curve walk is not compiled into it)
     if (scene_features(sc) == kFeatCurves && sc.bvh_has_bez && sc.bez_groups == 0 && claim && curve_blocks() > 0) {
         // resident blocks only: later blocks would find the rays claimed.  The BVH4 walk's LDS stack column
         // holds lds4 entries per lane (the rest in the overflow area).  Occupancy per (device, LDS bytes)
         const size_t clds = (size_t)256 * (size_t)(sc.lds4 > 0 ? sc.lds4 : 1) * sizeof(uint32_t);
+        const CurveKernel k = curve_kernel(rp, fuse);
         uint32_t occ_blocks = 0;
-        const void* kf = !fuse ? reinterpret_cast<const void*>(&k_extend_curves<0>)
-                       : rp.exact_libm ? reinterpret_cast<const void*>(&k_extend_curves<2>)
-                                       : reinterpret_cast<const void*>(&k_extend_curves<1>);
-        HIP_RETURN_IF(curve_occupancy(kf, clds, &occ_blocks));
+        if (const hipError_t e = curve_occupancy(k, clds, &occ_blocks)) return e;
         uint32_t pb = blocks < occ_blocks ? blocks : occ_blocks;
         if (pb > curve_blocks()) pb = curve_blocks();
         // the overflow area holds sc.ovf_lanes lanes per render lane: never launch more (ovf_lane indexes it)
         if (sc.stk_ovf && pb > sc.ovf_lanes / 256u) pb = sc.ovf_lanes / 256u;
         if (pb > sc.ring_waves / 4u) pb = sc.ring_waves / 4u;   // one survivor ring per wave
         if (pb == 0u) pb = 1u;
-        HIP_RETURN_IF(hipMemsetAsync(claim, 0, sizeof(unsigned int), s));
-        if (!fuse) {
-            hipLaunchKernelGGL((k_extend_curves<0>), dim3(pb), dim3(256), clds, s, sc, rp, st, in, n, hit,
-                               shard_cap, counts, depth0, claim, CurveFuse{});
-        } else if (rp.exact_libm) {
-            hipLaunchKernelGGL((k_extend_curves<2>), dim3(pb), dim3(256), clds, s, sc, rp, st, in, n, hit,
-                               shard_cap, counts, false, claim, *fuse);
-        } else {
-            hipLaunchKernelGGL((k_extend_curves<1>), dim3(pb), dim3(256), clds, s, sc, rp, st, in, n, hit,
-                               shard_cap, counts, false, claim, *fuse);
-        }
+        if (const hipError_t e = hipMemsetAsync(claim, 0, sizeof(unsigned int), s)) return e;
+        hipLaunchKernelGGL(k, dim3(pb), dim3(256), clds, s, sc, rp, st, in, n, hit, shard_cap, counts,
+                           fuse ? false : depth0, claim, fuse ? *fuse : CurveFuse{});
         return hipGetLastError();
     }
     if (fuse) return hipErrorNotSupported;           // only the persistent curve kernel shades its own hits
-#define RT_EXTEND_F(F)                                                                                      \
-    hipLaunchKernelGGL((k_extend<F>), dim3(blocks), dim3(256), lds, s, sc, rp, st, in, n, hit,             \
-                       shard_cap, counts, depth0)
-    switch (scene_features(sc)) {
-    case 0: RT_EXTEND_F(0); break;
-    case 1: RT_EXTEND_F(1); break;
-    case 2: RT_EXTEND_F(2); break;
-    default: RT_EXTEND_F(3); break;
-    }
-#undef RT_EXTEND_F
+    hipLaunchKernelGGL(extend_kernel(sc), dim3(blocks), dim3(256), lane_stack_lds(sc), s, sc, rp, st, in, n, hit,
+                       shard_cap, counts, depth0);
     return hipGetLastError();
 }
 hipError_t launch_hit_rays(const DevScene& sc, const double* rays, uint32_t n, double* out_t, int32_t* out_mat,
                            hipStream_t s) {
     const uint32_t blocks = (n + 255u) / 256u;
-    const size_t lds = (size_t)256 * (size_t)(sc.lane_stack > 0 ? sc.lane_stack : 1) * sizeof(uint32_t);
     if (!blocks) return hipSuccess;
-    switch (scene_features(sc)) {
-    case 0: hipLaunchKernelGGL((k_hit_rays<0>), dim3(blocks), dim3(256), lds, s, sc, rays, n, out_t, out_mat); break;
-    default:
-        hipLaunchKernelGGL((k_hit_rays<kFeatCurves | kFeatExtra>), dim3(blocks), dim3(256), lds, s, sc, rays, n, out_t,
-                           out_mat);
-        break;
-    }
+    hipLaunchKernelGGL(hit_rays_kernel(sc), dim3(blocks), dim3(256), lane_stack_lds(sc), s, sc, rays, n, out_t, out_mat);
     return hipGetLastError();
 }
 hipError_t launch_features(const DevScene& sc, const RenderParams& rp, uint32_t S, double* feat, hipStream_t s) {
     const uint32_t blocks = (rp.npix + 255u) / 256u;
     if (!blocks || !S) return hipSuccess;
-    const int tl = scene_tex_level(sc);
-    const size_t lds = (size_t)256 * (size_t)(sc.lane_stack > 0 ? sc.lane_stack : 1) * sizeof(uint32_t) +
-                       ((tl >= kTexPerlin && sc.has_perlin) ? sizeof(PerlinLds) : 0);
-#define RT_FEATURES_F(F)                                                                                           \
-    do {                                                                                                           \
-        if (tl == kTexImage) hipLaunchKernelGGL((k_features<F, kTexImage>), dim3(blocks), dim3(256), lds, s, sc, rp, S, feat); \
-        else if (tl == kTexPerlin) hipLaunchKernelGGL((k_features<F, kTexPerlin>), dim3(blocks), dim3(256), lds, s, sc, rp, S, feat); \
-        else hipLaunchKernelGGL((k_features<F, kTexPlain>), dim3(blocks), dim3(256), lds, s, sc, rp, S, feat);    \
-    } while (0)
-    switch (scene_features(sc)) {
-    case 0: RT_FEATURES_F(0); break;
-    case 1: RT_FEATURES_F(1); break;
-    case 2: RT_FEATURES_F(2); break;
-    default: RT_FEATURES_F(3); break;
-    }
-#undef RT_FEATURES_F
+    const size_t lds = lane_stack_lds(sc) +
+                       ((scene_tex_level(sc) >= kTexPerlin && sc.has_perlin) ? sizeof(PerlinLds) : 0);
+    hipLaunchKernelGGL(features_kernel(sc), dim3(blocks), dim3(256), lds, s, sc, rp, S, feat);
     return hipGetLastError();
 }
 // bytes of LDS k_extend_lds needs for the scene's time-0 tree (0 = cannot run)
@@ -3462,46 +3437,32 @@ size_t extend_lds_bytes(const DevScene& sc) {
     if (sc.n_fbvh2 >= 32768 || sc.n_fbleaf >= 32768) return 0;        // 16-bit stack entries
     return extend_lds_need(sc);
 }
-// the kernel instance a scene's LDS launches use (SOLO: the world is one BVH group)
-static const void* extend_lds_fn(const DevScene& sc) {
-    return sc.bvh_solo ? reinterpret_cast<const void*>(&k_extend_lds<true>)
-                       : reinterpret_cast<const void*>(&k_extend_lds<false>);
-}
-static const void* camera_fn(const DevScene& sc) {
-    if (sc.tree0_any_time)
-        return sc.bvh_solo ? reinterpret_cast<const void*>(&k_camera<false, true>)
-                           : reinterpret_cast<const void*>(&k_camera<false, false>);
-    return sc.bvh_solo ? reinterpret_cast<const void*>(&k_camera<true, true>)
-                       : reinterpret_cast<const void*>(&k_camera<true, false>);
+// the grid of a persistent LDS kernel over n items
+static uint32_t lds_grid(const uint32_t n, const uint32_t max_blocks) {
+    const uint32_t blocks = (n + kExtLdsBlock - 1) / kExtLdsBlock;
+    return shard_blocks(blocks > max_blocks ? max_blocks : blocks);
 }
 hipError_t launch_extend_lds(const DevScene& sc, const RenderParams& rp, const PathState& st, const QView& in,
                              uint32_t n, const HitBuf& hit,
                              uint32_t shard_cap, uint32_t* counts, uint32_t max_blocks, unsigned long long* err,
                              hipStream_t s) {
     const size_t lds = extend_lds_bytes(sc);
-    uint32_t blocks = (n + kExtLdsBlock - 1) / kExtLdsBlock;
-    if (blocks > max_blocks) blocks = max_blocks;
-    blocks = (blocks + kShards - 1) / kShards * kShards;      // every shard gets the same number of blocks
-    if (sc.bvh_solo)
-        hipLaunchKernelGGL(k_extend_lds<true>, dim3(blocks), dim3(kExtLdsBlock), lds, s, sc, rp, st, in, n, hit,
-                           shard_cap, counts, (uint32_t)lds, err);
-    else
-        hipLaunchKernelGGL(k_extend_lds<false>, dim3(blocks), dim3(kExtLdsBlock), lds, s, sc, rp, st, in, n, hit,
-                           shard_cap, counts, (uint32_t)lds, err);
+    hipLaunchKernelGGL(extend_lds_kernel(sc), dim3(lds_grid(n, max_blocks)), dim3(kExtLdsBlock), lds, s, sc, rp, st, in,
+                       n, hit, shard_cap, counts, (uint32_t)lds, err);
     return hipGetLastError();
 }
 // resident blocks of a persistent LDS kernel: every block it can keep on the device at once
 static hipError_t resident_blocks(const void* f, size_t lds, uint32_t* max_blocks) {
-    HIP_RETURN_IF(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
     int dev = 0, cus = 0, per_cu = 0;
-    HIP_RETURN_IF(hipGetDevice(&dev));
-    HIP_RETURN_IF(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    HIP_RETURN_IF(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, kExtLdsBlock, lds));
+    if (const hipError_t e = hipGetDevice(&dev)) return e;
+    if (const hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) return e;
+    if (const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, kExtLdsBlock, lds)) return e;
     *max_blocks = (uint32_t)(cus * (per_cu > 0 ? per_cu : 0));
     return hipSuccess;
 }
 hipError_t extend_lds_prepare(const DevScene& sc, size_t lds, uint32_t* max_blocks) {
-    return resident_blocks(extend_lds_fn(sc), lds, max_blocks);
+    return resident_blocks(reinterpret_cast<const void*>(extend_lds_kernel(sc)), lds, max_blocks);
 }
 // LDS bytes k_camera needs (0 = cannot run): the all-times tree when the scene
 // has moving spheres, else the time-0 tree
@@ -3512,39 +3473,23 @@ size_t camera_lds_bytes(const DevScene& sc) {
     return camera_lds_need(sc);
 }
 hipError_t camera_prepare(const DevScene& sc, size_t lds, uint32_t* max_blocks) {
-    return resident_blocks(camera_fn(sc), lds, max_blocks);
+    return resident_blocks(reinterpret_cast<const void*>(camera_kernel(sc)), lds, max_blocks);
 }
 hipError_t launch_camera(const DevScene& sc, const RenderParams& rp, const PathState& st, uint32_t n,
                          const HitBuf& hit, uint32_t shard_cap, uint32_t* counts,
                          size_t lds, uint32_t max_blocks, unsigned long long* err, hipStream_t s) {
-    uint32_t blocks = (n + kExtLdsBlock - 1) / kExtLdsBlock;
-    if (blocks > max_blocks) blocks = max_blocks;
-    blocks = (blocks + kShards - 1) / kShards * kShards;
-#define RT_CAMERA(A, S)                                                                                       \
-    hipLaunchKernelGGL((k_camera<A, S>), dim3(blocks), dim3(kExtLdsBlock), lds, s, sc, rp, st, n, hit,          \
-                       shard_cap, counts, (uint32_t)lds, err)
-    if (sc.tree0_any_time) { if (sc.bvh_solo) RT_CAMERA(false, true); else RT_CAMERA(false, false); }
-    else { if (sc.bvh_solo) RT_CAMERA(true, true); else RT_CAMERA(true, false); }
-#undef RT_CAMERA
+    hipLaunchKernelGGL(camera_kernel(sc), dim3(lds_grid(n, max_blocks)), dim3(kExtLdsBlock), lds, s, sc, rp, st, n, hit,
+                       shard_cap, counts, (uint32_t)lds, err);
     return hipGetLastError();
 }
-// the probe's instance for a scene: the one launch_extend_lds (time0) / launch_camera picks of its kernel
 hipError_t launch_hit_rays_lds(const DevScene& sc, bool time0, size_t lds, const double* rays, uint32_t n,
                                double* out_t, int32_t* out_mat, hipStream_t s) {
     uint32_t blocks = (n + kExtLdsBlock - 1) / kExtLdsBlock;
     if (!blocks) return hipSuccess;
     if (blocks > 1024u) blocks = 1024u;                  // grid-stride, as the persistent kernels
-#define RT_HIT_LDS(T, A, S)                                                                                   \
-    do {                                                                                                      \
-        HIP_RETURN_IF(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hit_rays_lds<T, A, S>),            \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));             \
-        hipLaunchKernelGGL((k_hit_rays_lds<T, A, S>), dim3(blocks), dim3(kExtLdsBlock), lds, s, sc, rays, n,   \
-                           out_t, out_mat, (uint32_t)lds);                                                    \
-    } while (0)
-    if (time0) { if (sc.bvh_solo) RT_HIT_LDS(true, false, true); else RT_HIT_LDS(true, false, false); }
-    else if (sc.tree0_any_time) { if (sc.bvh_solo) RT_HIT_LDS(false, false, true); else RT_HIT_LDS(false, false, false); }
-    else { if (sc.bvh_solo) RT_HIT_LDS(false, true, true); else RT_HIT_LDS(false, true, false); }
-#undef RT_HIT_LDS
+    const HitRaysLdsKernel k = hit_rays_lds_kernel(sc, time0);
+    if (const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(kExtLdsBlock), lds, s, sc, rays, n, out_t, out_mat, (uint32_t)lds);
     return hipGetLastError();
 }
 constexpr size_t kShadeLeafLds = 32768;      // stage the leaf records when they fit (256 leaves)
@@ -3557,52 +3502,17 @@ hipError_t launch_shade(int mat, const DevScene& sc, const DevScene* scd, const 
     // (rt_api's shard slack assumes <= 4096, a multiple of 8).  2048 / 4096 blocks for the sparse metal /
     // dielectric queues measured the same as 1024 (profiles/r03/ab/ab_sparse_grid.log)
     constexpr uint32_t max_blocks = 1024;
-    uint32_t blocks = (n_upper + 255u) / 256u;
-    blocks = (blocks + kShards - 1) / kShards * kShards;     // every shard gets the same number of blocks
+    uint32_t blocks = shard_blocks((n_upper + 255u) / 256u);
     if (blocks > max_blocks) blocks = max_blocks;
     if (blocks == 0u) blocks = kShards;
     const HitRec* hq = hit.h + (size_t)mat * hit.stride;
-#define RT_SHADE_EX(M, TL, LS, EX)                                                                           \
-    do {                                                                                                     \
-        if (ll)                                                                                              \
-            hipLaunchKernelGGL((k_shade<M, TL, LS, true, EX>), dim3(blocks), dim3(256), lds, s, scd, rp, in,   \
-                               hq, qv, out, out_counts, shard_cap, depth);                                   \
-        else                                                                                                 \
-            hipLaunchKernelGGL((k_shade<M, TL, LS, false, EX>), dim3(blocks), dim3(256), lds, s, scd, rp, in,  \
-                               hq, qv, out, out_counts, shard_cap, depth);                                   \
-    } while (0)
-    // libm's own sin / cos for the bounce directions (bounce_cos_sin: RT_OPT_EXACT_LIBM, by default in
-    // scenes with curves); only the lambertian kernels draw directions with them
-#define RT_SHADE(M, TL, LS)                                                                                  \
-    do {                                                                                                     \
-        if (M == MAT_LAMBERTIAN && rp.exact_libm) RT_SHADE_EX(M, TL, LS, true);                             \
-        else RT_SHADE_EX(M, TL, LS, false);                                                                  \
-    } while (0)
-    // the scene's texture level (scenes with image textures take the kTexImage instances, the others keep theirs)
-#define RT_SHADE_TL(M, LS)                                                                                   \
-    do {                                                                                                     \
-        if (tl == kTexImage) RT_SHADE(M, kTexImage, LS);                                                     \
-        else if (tl == kTexPerlin) RT_SHADE(M, kTexPerlin, LS);                                              \
-        else RT_SHADE(M, kTexPlain, LS);                                                                     \
-    } while (0)
-    const int tl = scene_tex_level(sc);
-    const bool pn = tl >= kTexPerlin;
-    const bool ls = sc.light.type != LIGHT_OFF;       // only lambertian scatter uses the light mixture
     const size_t leaf_lds = (size_t)sc.n_leaves * sizeof(LeafInfo);
     const bool ll = leaf_lds <= kShadeLeafLds;
     // kTexPerlin / kTexImage kernels of every material carry the Perlin tables (metal albedo may be a noise texture)
+    const bool pn = scene_tex_level(sc) >= kTexPerlin;
     const size_t lds = (ll ? leaf_lds : 0) + ((pn && mat != MAT_DIELECTRIC && sc.has_perlin) ? sizeof(PerlinLds) : 0);
-    switch (mat) {
-    case MAT_LAMBERTIAN:
-        if (ls) RT_SHADE_TL(MAT_LAMBERTIAN, true); else RT_SHADE_TL(MAT_LAMBERTIAN, false);
-        break;
-    case MAT_METAL: RT_SHADE_TL(MAT_METAL, false); break;
-    case MAT_DIELECTRIC: RT_SHADE(MAT_DIELECTRIC, kTexPlain, false); break;      // attenuation is constant 1
-    default: RT_SHADE_TL(MAT_DIFFUSE_LIGHT, false); break;
-    }
-#undef RT_SHADE_TL
-#undef RT_SHADE
-#undef RT_SHADE_EX
+    hipLaunchKernelGGL(shade_kernel(mat, sc, rp, ll), dim3(blocks), dim3(256), lds, s, scd, rp, in, hq, qv, out,
+                       out_counts, shard_cap, depth);
     return hipGetLastError();
 }
 hipError_t launch_finish(const DevScene& sc, const DevScene* scd, const RenderParams& rp, const PathState& st, const QView& in,
@@ -3616,55 +3526,12 @@ hipError_t launch_finish(const DevScene& sc, const DevScene* scd, const RenderPa
     // SOLO tail: plain-sphere world in one BVH, its time-0 tree in LDS, child refs within int16
     const bool solo = tree0_lds && sc.bvh_solo && scene_features(sc) == 0 && extend_lds_bytes(sc) > 0 &&
                       sc.n_bvh2 < 32768 && sc.n_bleaf < 32768 && !finish_generic();
-    const size_t stack_entry = solo ? sizeof(uint16_t) : sizeof(uint32_t);
-    size_t lds = ((size_t)256 * (size_t)(sc.lane_stack > 0 ? sc.lane_stack : 1) * stack_entry + 15) / 16 * 16;
+    size_t lds = (lane_stack_lds(sc, solo ? sizeof(uint16_t) : sizeof(uint32_t)) + 15) / 16 * 16;
     if (tree0_lds) lds += solo ? tree - (size_t)sc.n_fbleaf * sizeof(BvhLeaf) : tree;
     // the Perlin tables ride at the end of the dynamic LDS, only where they are staged (TL >= kTexPerlin and tables given)
-    const size_t perlin = sc.has_perlin ? sizeof(PerlinLds) : 0;
-    // the bounce directions' sin / cos (RT_OPT_EXACT_LIBM): rt_libm.h's or the device library's
-    const bool ex = rp.exact_libm != 0;
-#define RT_FINISH_F(F) do { if (tl == kTexImage) RT_FINISH(F, kTexImage, true); else RT_FINISH(F, kTexPerlin, true); } while (0)
-#define RT_FINISH_SOLO_EX(TL, LS, EX) \
-    hipLaunchKernelGGL((k_finish<0, TL, LS, true, EX>), dim3(blocks), dim3(256), lds + (TL >= kTexPerlin ? perlin : 0), s, scd, rp, st, \
-                       in, n, seg_count, tree0_lds, depth)
-#define RT_FINISH_EX(F, TL, LS, EX) \
-    hipLaunchKernelGGL((k_finish<F, TL, LS, false, EX>), dim3(blocks), dim3(256), lds + (TL >= kTexPerlin ? perlin : 0), s, scd, rp, st, \
-                       in, n, seg_count, tree0_lds, depth)
-#define RT_FINISH_SOLO(TL, LS) do { if (ex) RT_FINISH_SOLO_EX(TL, LS, true); else RT_FINISH_SOLO_EX(TL, LS, false); } while (0)
-#define RT_FINISH(F, TL, LS) do { if (ex) RT_FINISH_EX(F, TL, LS, true); else RT_FINISH_EX(F, TL, LS, false); } while (0)
-#define RT_FINISH_SOLO_TL(LS) \
-    do { \
-        if (tl == kTexImage) RT_FINISH_SOLO(kTexImage, LS); \
-        else if (tl == kTexPerlin) RT_FINISH_SOLO(kTexPerlin, LS); \
-        else RT_FINISH_SOLO(kTexPlain, LS); \
-    } while (0)
-#define RT_FINISH_TL(LS) \
-    do { \
-        if (tl == kTexImage) RT_FINISH(0, kTexImage, LS); \
-        else if (tl == kTexPerlin) RT_FINISH(0, kTexPerlin, LS); \
-        else RT_FINISH(0, kTexPlain, LS); \
-    } while (0)
-    // the plain-sphere feature set also gets Perlin / light-mixture specialisations:
-    // the tail kernel carries every material's code, so dropping the unused ones
-    // trims its register file
-    const int tl = scene_tex_level(sc);
-    const bool ls = sc.light.type != LIGHT_OFF;
-    switch (scene_features(sc)) {
-    case 0:
-        if (solo) { if (ls) RT_FINISH_SOLO_TL(true); else RT_FINISH_SOLO_TL(false); }
-        else { if (ls) RT_FINISH_TL(true); else RT_FINISH_TL(false); }
-        break;
-    case 1: RT_FINISH_F(1); break;
-    case 2: RT_FINISH_F(2); break;
-    default: RT_FINISH_F(3); break;
-    }
-#undef RT_FINISH_F
-#undef RT_FINISH_SOLO_TL
-#undef RT_FINISH_TL
-#undef RT_FINISH_SOLO
-#undef RT_FINISH
-#undef RT_FINISH_SOLO_EX
-#undef RT_FINISH_EX
+    if (finish_tex_level(sc) >= kTexPerlin && sc.has_perlin) lds += sizeof(PerlinLds);
+    hipLaunchKernelGGL(finish_kernel(sc, rp, solo), dim3(blocks), dim3(256), lds, s, scd, rp, st, in, n, seg_count,
+                       tree0_lds, depth);
     return hipGetLastError();
 }
 // test hooks (render_impl: RTAMD_REJECT_CAP / RTAMD_CURVE_RAY_CAP, tests only): the samplers' attempt
@@ -3673,15 +3540,15 @@ hipError_t set_test_caps(int reject_cap, uint32_t curve_ray_cap) {
     static int applied[64];                     // per device; 0 = not written yet (the defaults)
     static uint32_t applied_ray[64];
     int dev = 0;
-    HIP_RETURN_IF(hipGetDevice(&dev));
+    if (const hipError_t e = hipGetDevice(&dev)) return e;
     if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
     const int have = applied[dev] ? applied[dev] - 1 : kRejectCap;
     if (reject_cap != have) {
-        HIP_RETURN_IF(hipMemcpyToSymbol(HIP_SYMBOL(g_reject_cap), &reject_cap, sizeof reject_cap));
+        if (const hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_reject_cap), &reject_cap, sizeof reject_cap)) return e;
         applied[dev] = reject_cap + 1;
     }
     if (curve_ray_cap != applied_ray[dev]) {
-        HIP_RETURN_IF(hipMemcpyToSymbol(HIP_SYMBOL(g_curve_ray_cap), &curve_ray_cap, sizeof curve_ray_cap));
+        if (const hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_curve_ray_cap), &curve_ray_cap, sizeof curve_ray_cap)) return e;
         applied_ray[dev] = curve_ray_cap;
     }
     return hipSuccess;
@@ -3689,20 +3556,20 @@ hipError_t set_test_caps(int reject_cap, uint32_t curve_ray_cap) {
 // the device fault word: read and clear (render_impl, after the render's streams are synchronised)
 hipError_t take_fault(uint32_t* out) {
     uint32_t f = 0;
-    HIP_RETURN_IF(hipMemcpyFromSymbol(&f, HIP_SYMBOL(g_fault), sizeof f));
+    if (const hipError_t e = hipMemcpyFromSymbol(&f, HIP_SYMBOL(g_fault), sizeof f)) return e;
     if (f) {
         const uint32_t z = 0;
-        HIP_RETURN_IF(hipMemcpyToSymbol(HIP_SYMBOL(g_fault), &z, sizeof z));
+        if (const hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_fault), &z, sizeof z)) return e;
     }
     *out = f;
     return hipSuccess;
 }
 // the batched-curve counters: read and clear (render_impl, at the start and end of a render)
 hipError_t take_curve_stats(unsigned long long out[2]) {
-    HIP_RETURN_IF(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_curve_stats), 2 * sizeof(unsigned long long)));
+    if (const hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_curve_stats), 2 * sizeof(unsigned long long))) return e;
     if (out[0] || out[1]) {
         const unsigned long long z[2] = {0ull, 0ull};
-        HIP_RETURN_IF(hipMemcpyToSymbol(HIP_SYMBOL(g_curve_stats), z, sizeof z));
+        if (const hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_curve_stats), z, sizeof z)) return e;
     }
     return hipSuccess;
 }
@@ -3710,7 +3577,7 @@ hipError_t take_curve_stats(unsigned long long out[2]) {
 extern "C" int rt_debug_stats(unsigned long long* out, int reset) {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stats), sizeof g_stats) != hipSuccess) return 1;
     if (reset) {
-        unsigned long long z[48] = {0};
+        unsigned long long z[kStatSlots] = {0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_stats), z, sizeof z) != hipSuccess) return 1;
     }
     return 0;

@@ -9,7 +9,7 @@
   tests/test_oracle_bvh.py).
 * Flat curves — converge's depth estimate negative, so the root is a leaf
   (bezier.scm:130,189-193) — pooled into the wavefront curve kernel's batched
-  subdivision (stage B over >= RT_BEZ_HOLD survivors), counted by
+  subdivision (stage B over >= kBezHold survivors), counted by
   rt_stats.curve_flat_pooled: the case whose negative leaf level faulted C5 in
   round 2 before the level was clamped at 0.
 * A curve needing more subdivision levels than the walk supports fails the
