@@ -151,8 +151,21 @@ int rt_add_translate(int scene, int obj, const double offset[3], int* out_obj); 
 int rt_add_rotate_y(int scene, int obj, double angle_deg, int* out_obj);                        /* g:rotate-y :483 */
 /* An object list (make-scene's obj-list, geometry.scm:52; a nested list). */
 int rt_add_list(int scene, const int* objs, int n, int* out_obj);
-/* g:make-bvh-node :226 / g:make-bvh-with-sah :294.  Closest-hit over the
- * children; the library builds its own acceleration structure. */
+/* g:make-bvh-node :226 / g:make-bvh-with-sah :294.  Closest-hit over the children, which are flattened into
+ * the world's list like any nested list: the node itself builds nothing.  At rt_scene_commit the library
+ * builds one tree of its own over leaves of the whole world (whether or not they were under an rt_add_bvh):
+ *   - world-level spheres and moving spheres (under no rt_add_translate / rt_add_rotate_y) listed before the
+ *     first constant medium, when there are at least RTAMD_BVH_MIN of them (environment, default 16), and
+ *     world-level curves with them;
+ *   - with RT_HAS_GENERIC_BVH, also rects (box faces included) under any instance chain or none, and spheres
+ *     and moving spheres under an instance chain, whose world-space box is finite — when the scene has at
+ *     least RTAMD_BVH_GENERIC_MIN such leaves (environment, read at commit; default 48) and
+ *     holds no curve, no constant medium (so no medium boundary) and no Klein set.  Scenes with any of those
+ *     are committed exactly as without RT_HAS_GENERIC_BVH.  Rects under more than 16 distinct rotations: the
+ *     rects of the 17th rotation on stay outside the tree.
+ * Every other leaf is tested one by one for every ray segment, grouped by instance chain and type
+ * (rt_tree_info.group_leaves counts them).  Whatever the tree takes, the closest hit is hit-obj-list's
+ * (geometry.scm:33-50) over the flattened list, ties at one t included. */
 int rt_add_bvh(int scene, const int* objs, int n, double time0, double time1, int sah, int* out_obj);
 
 /* camera — cam:make-camera (camera.scm:63-78) evaluated on the host side;
@@ -350,6 +363,24 @@ typedef struct rt_scene_info {
     int32_t  tree0_any_time;  /* 1: no moving spheres in the world BVH, so its time-0 tree serves rays of every time (was reserved0) */
 } rt_scene_info;
 int rt_get_scene_info(int scene, rt_scene_info* out);
+
+/* Which leaves of a committed scene the world tree took (rt_add_bvh above).  rt_scene_info keeps its layout;
+ * RT_ABI_VERSION stays 7; test RT_HAS_GENERIC_BVH for this entry point.  A scene whose tree holds generic
+ * leaves walks it in device memory only: its rt_scene_info reports extend_lds_bytes = camera_lds_bytes = 0
+ * and rt_hit_rays_walk refuses the LDS walks. */
+typedef struct rt_tree_info {
+    int32_t  sphere_leaves;   /* world-level spheres and moving spheres in the tree */
+    int32_t  curve_leaves;    /* world-level curves in the tree */
+    int32_t  generic_leaves;  /* generic leaves in the tree: rects, and spheres / moving spheres under a chain */
+    int32_t  group_leaves;    /* leaves outside the tree, in brute-force groups (constant media included) */
+    int32_t  nodes, depth;    /* the all-times tree: inner nodes, deepest level */
+    int32_t  nodes0, depth0;  /* the time-0 tree (0, 0: none) */
+    int32_t  rot_entries;     /* distinct rotations among the tree rects' chains (no rotation counts as one) */
+    int32_t  generic_min;     /* RTAMD_BVH_GENERIC_MIN in force at the commit */
+    int32_t  reserved[6];
+} rt_tree_info;
+#define RT_HAS_GENERIC_BVH 1
+int rt_get_tree_info(int scene, rt_tree_info* out);
 /* Record per-kernel HIP events during renders (adds a little host overhead). */
 int rt_set_profiling(int scene, int enabled);
 

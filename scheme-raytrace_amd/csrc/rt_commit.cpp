@@ -16,6 +16,7 @@
 #include "rt_host.h"
 #include "rt_launch.h"
 #include "rt_bvh.h"
+#include "rt_leafbox.h"
 
 using namespace rtamd;
 
@@ -112,6 +113,17 @@ int bvh_sweep_max(const bool curves) {
 size_t bvh_min_prims() {
     const char* e = std::getenv("RTAMD_BVH_MIN");
     return e ? (size_t)std::strtoull(e, nullptr, 10) : 16;
+}
+
+// fewest generic leaves (rects, instanced spheres) a scene needs for them to join the world tree: below
+// the crossover a handful of uniform group loops beats a per-lane walk (the default is
+// the measured crossover, 48 leaves, and never below 32; the environment may set any count, for measurements and tests)
+constexpr size_t kGenericMinDefault = 48;
+static_assert(kGenericMinDefault >= 32, "every scene with fewer generic leaves keeps its groups");
+size_t bvh_generic_min() {
+    const char* e = std::getenv("RTAMD_BVH_GENERIC_MIN");
+    const size_t v = e ? (size_t)std::strtoull(e, nullptr, 10) : kGenericMinDefault;
+    return std::min<size_t>(std::max<size_t>(v, 1), (size_t)1 << 30);
 }
 
 // device time commit_scene spends in upload() (allocation + copy), for rt_scene_info's split of the
@@ -285,10 +297,79 @@ int commit_scene(Scene* s, int world) {
     COMMIT_MARK("flatten");
     const int threads = build_threads();
     std::vector<int> in_bvh;                         // the leaves the BVH takes, in list order
+    size_t n_world = 0;                              // of them, world-level spheres / moving spheres / curves
     for (size_t i = 0; i < f.leaves.size(); ++i) {
         const LeafTmp& L = f.leaves[i];
         if (seg[i] == 0 && L.chain == -1 && (L.type == LEAF_SPHERE || L.type == LEAF_MSPHERE || L.type == LEAF_BEZIER))
             in_bvh.push_back((int)i);
+    }
+    n_world = in_bvh.size();
+    // Generic tree leaves (include/rt.h, rt_add_bvh): rects under any chain or none and spheres / moving
+    // spheres under a chain, with a finite world-space box (rt_leafbox.h), in scenes of spheres, moving
+    // spheres and rects only.  A rect also needs its chain's rotation in the table the kernels test a
+    // ray's direction against (RotEntry; at most kMaxRot).  They join the tree when there are at least
+    // bvh_generic_min() of them and the tree is built at all; else nothing below differs from a commit
+    // without them.
+    const double cam_tlo = std::min(std::min(s->cam[22], s->cam[23]), 0.0);
+    const double cam_thi = std::max(std::max(s->cam[22], s->cam[23]), 0.0);
+    auto leaf_geom = [&](const LeafTmp& L) {
+        const Obj& o = s->objs[L.obj];
+        LeafGeom g{};
+        g.type = L.type;
+        for (int k = 0; k < 3; ++k) { g.c0[k] = o.c0[k]; g.c1[k] = o.c1[k]; }
+        g.r = o.r; g.t0 = o.t0; g.t1 = o.t1;
+        g.a0 = o.a0; g.a1 = o.a1; g.b0 = o.b0; g.b1 = o.b1; g.k = o.k;
+        return g;
+    };
+    auto chain_ops = [&](const int ch, int& n) -> const ChainOpRec* {
+        n = ch >= 0 ? (int)f.chains[ch].size() : 0;
+        return ch >= 0 ? f.chains[ch].data() : nullptr;
+    };
+    const size_t gen_min = bvh_generic_min();
+    std::vector<RotEntry> rot;
+    std::vector<PrimRef> gen_ref;                    // a generic leaf's box, by list position
+    std::vector<char> is_gen;
+    size_t n_gen = 0;
+    bool plain = nseg == 1 && f.bounds.empty();
+    for (const LeafTmp& L : f.leaves) plain = plain && L.type != LEAF_BEZIER && L.type != LEAF_KLEIN && L.type != LEAF_MEDIUM;
+    if (plain && f.leaves.size() >= gen_min) {
+        gen_ref.resize(f.leaves.size());
+        is_gen.assign(f.leaves.size(), 0);
+        for (size_t i = 0; i < f.leaves.size(); ++i) {
+            const LeafTmp& L = f.leaves[i];
+            const bool is_rect = L.type >= LEAF_RECT_XY && L.type <= LEAF_RECT_YZ;
+            if (!is_rect && L.chain < 0) continue;
+            int n_ops = 0;
+            const ChainOpRec* ops = chain_ops(L.chain, n_ops);
+            PrimRef r{};
+            if (!leaf_world_box(leaf_geom(L), ops, n_ops, cam_tlo, cam_thi, r.lo, r.hi)) continue;
+            if (is_rect) {
+                RotEntry e{};
+                for (int k = 0; k < n_ops; ++k)
+                    if (ops[k].op == OP_ROTATE_Y) { e.sc[e.n][0] = ops[k].x; e.sc[e.n][1] = ops[k].y; ++e.n; }
+                size_t at = 0;
+                while (at < rot.size() && (rot[at].n != e.n || std::memcmp(rot[at].sc, e.sc, sizeof e.sc) != 0)) ++at;
+                if (at == rot.size()) {
+                    if (rot.size() >= (size_t)kMaxRot) continue;       // the table is full: the rect keeps its group
+                    rot.push_back(e);
+                }
+                rot[at].axes |= L.type == LEAF_RECT_YZ ? 1 : L.type == LEAF_RECT_XZ ? 2 : 4;   // the plane's normal
+            }
+            for (int k = 0; k < 3; ++k) r.c[k] = 0.5 * (r.lo[k] + r.hi[k]);
+            r.leaf = (int)i;
+            r.type = L.type;
+            gen_ref[i] = r;
+            is_gen[i] = 1;
+            ++n_gen;
+        }
+    }
+    const bool generic = n_gen > 0 && n_gen >= gen_min && n_world + n_gen >= bvh_min_prims();
+    if (generic) {
+        in_bvh.clear();
+        for (size_t i = 0; i < f.leaves.size(); ++i) {
+            const LeafTmp& L = f.leaves[i];
+            if (is_gen[i] || (L.chain == -1 && (L.type == LEAF_SPHERE || L.type == LEAF_MSPHERE))) in_bvh.push_back((int)i);
+        }
     }
     std::vector<PrimRef> refs(in_bvh.size());
     parallel_for(in_bvh.size(), threads, [&](const size_t jb, const size_t je) {
@@ -296,6 +377,7 @@ int commit_scene(Scene* s, int world) {
         const size_t i = (size_t)in_bvh[j];
         const LeafTmp& L = f.leaves[i];
         const Obj& o = s->objs[L.obj];
+        if (generic && is_gen[i]) { refs[j] = gen_ref[i]; continue; }
         PrimRef r{};
         r.leaf = (int)i;
         r.type = L.type;
@@ -349,6 +431,12 @@ int commit_scene(Scene* s, int world) {
     int32_t fbvh2_root = 0;
     bool tree0_any_time = false;
     bool tree0_direct = false;
+    // generic tree leaves: (type, local) of ref i, then of the time-0 tree's ref i (-> DevScene::gleaf);
+    // the time-0 tree itself
+    std::vector<std::pair<int, int>> gsrc;
+    HostVec<BvhNode2> g0bvh2;
+    HostVec<BvhLeaf> g0bleaf;
+    int32_t g0bvh2_root = 0, depth_all = 0, depth0 = 0;
     if (use_bvh) {
         BvhBuild bb{refs, {}};
         // one primitive per leaf (measured fastest for sphere trees; for C5's curve tree, with the exact
@@ -381,8 +469,10 @@ int commit_scene(Scene* s, int world) {
         bvh_pad = (float)margin;
         COMMIT_MARK("radius");
         flatten_bvh2(bvh_nodes, margin, [&](int b, int e) {
+            if (generic) return BvhLeaf{0, 0, 0, 0, 0, 0, b, e - b};      // every leaf by its id (gleaf)
             return BvhLeaf{ns[b], ns[e] - ns[b], nm[b], nm[e] - nm[b], nb[b], nb[e] - nb[b], 0, 0};
         }, bvh2, bleaf, bvh2_root, lane_stack, threads);
+        depth_all = lane_stack;
         COMMIT_MARK("flatten2");
         if (bvh_has_bez) {                               // single-curve leaves: direct refs (kDirectCurve)
             auto direct = [&](int32_t& ref) {
@@ -409,7 +499,8 @@ int commit_scene(Scene* s, int world) {
                 const LeafTmp& L = f.leaves[r.leaf];
                 const Obj& o = s->objs[L.obj];
                 LeafInfo li{};
-                li.type = L.type; li.chain = -1; li.mat = o.mat; li.flip = L.flip;
+                li.type = L.type; li.chain = L.chain; li.mat = o.mat; li.flip = L.flip;
+                if (r.type >= LEAF_RECT_XY && r.type <= LEAF_RECT_YZ) continue;      // (generic: below)
                 if (r.type == LEAF_SPHERE) {
                     li.inv_r = 1.0 / o.r;
                     li.local = ns[i];
@@ -434,6 +525,56 @@ int commit_scene(Scene* s, int world) {
                 ord_local[(size_t)r.leaf] = li.local;
             }
         });
+        if (generic) {
+            gsrc.resize(refs.size());
+            for (size_t i = 0; i < refs.size(); ++i) {
+                const PrimRef& r = refs[i];
+                if (r.type == LEAF_SPHERE) { gsrc[i] = {LEAF_SPHERE, ns[i]}; continue; }
+                if (r.type == LEAF_MSPHERE) { gsrc[i] = {LEAF_MSPHERE, nm[i]}; continue; }
+                const LeafTmp& L = f.leaves[r.leaf];                          // a rect: records in refs order
+                const Obj& o = s->objs[L.obj];
+                LeafInfo li{};
+                li.type = L.type; li.chain = L.chain; li.mat = o.mat; li.flip = L.flip;
+                li.local = (int)rect.size();
+                RectRec R{};
+                R.a0 = o.a0; R.a1 = o.a1; R.b0 = o.b0; R.b1 = o.b1; R.k = o.k;
+                rect.push_back(R);
+                lrect[L.type - LEAF_RECT_XY].push_back(li);
+                ord_type[(size_t)r.leaf] = L.type;
+                ord_local[(size_t)r.leaf] = li.local;
+                gsrc[i] = {L.type, li.local};
+            }
+            // The time-0 tree of a scene with generic leaves: the same leaves, every moving sphere (under a
+            // chain or not) bounded where it is at time 0; none when no sphere moves.  A moving sphere's
+            // test at time +0.0 is the all-times one, so only the boxes differ.
+            if (nm[refs.size()] > 0 && !std::getenv("RTAMD_NO_BVH0")) {
+                std::vector<PrimRef> refs0(refs);
+                for (size_t i = 0; i < refs0.size(); ++i) {
+                    PrimRef& r = refs0[i];
+                    const LeafTmp& L = f.leaves[r.leaf];
+                    r.leaf = (int)i;                                          // index into refs (-> gsrc)
+                    if (r.type != LEAF_MSPHERE) continue;
+                    int n_ops = 0;
+                    const ChainOpRec* ops = chain_ops(L.chain, n_ops);
+                    double lo[3], hi[3];
+                    if (!leaf_world_box(leaf_geom(L), ops, n_ops, 0.0, 0.0, lo, hi)) continue;   // keeps the all-times box
+                    for (int k = 0; k < 3; ++k) { r.lo[k] = lo[k]; r.hi[k] = hi[k]; r.c[k] = 0.5 * (lo[k] + hi[k]); }
+                }
+                BvhBuild b0{refs0, {}};
+                b0.leaf_max = bb.leaf_max;
+                b0.trav_cost = bb.trav_cost;
+                b0.sweep_max = bb.sweep_max;
+                b0.threads = bb.threads;
+                const auto t0s = std::chrono::steady_clock::now();
+                b0.build(0, (int)refs0.size(), 0);
+                s->commit_sah_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0s).count();
+                const int nr = (int)refs.size();
+                flatten_bvh2(b0.nodes, margin, [&](int b, int e) { return BvhLeaf{0, 0, 0, 0, 0, 0, nr + b, e - b}; },
+                             g0bvh2, g0bleaf, g0bvh2_root, depth0);
+                lane_stack = std::max(lane_stack, depth0);
+                for (const PrimRef& r : refs0) gsrc.push_back(gsrc[(size_t)r.leaf]);
+            }
+        }
         // Time-0 BVH.  Every scattered ray has time 0 (make-ray, ray.scm:8-9,
         // Q4), so for those rays a moving sphere sits at center(0) exactly:
         // the second tree bounds each moving sphere at that one position
@@ -444,7 +585,7 @@ int commit_scene(Scene* s, int world) {
         // (Built for every sphere tree: with no moving spheres it equals the
         // all-times tree and serves every ray, tree0_any_time.)
         tree0_any_time = nm[refs.size()] == 0;
-        if (!bvh_has_bez && !std::getenv("RTAMD_NO_BVH0")) {
+        if (!bvh_has_bez && !generic && !std::getenv("RTAMD_NO_BVH0")) {
             std::vector<PrimRef> refs0;
             for (size_t i = 0; i < refs.size(); ++i) {
                 PrimRef r = refs[i];
@@ -487,7 +628,8 @@ int commit_scene(Scene* s, int world) {
                 }
             }
             flatten_bvh2(b0.nodes, margin, [&](int b, int e) { return BvhLeaf{b, e - b, 0, 0, 0, 0, 0, 0}; },
-                         fbvh2, fbleaf, fbvh2_root, lane_stack);
+                         fbvh2, fbleaf, fbvh2_root, depth0);
+            lane_stack = std::max(lane_stack, depth0);
             // Direct leaves: when every time-0 leaf holds exactly one sphere, put
             // fsph (and its leaf-id map) in leaf order, so leaf k is sphere k and
             // the SOLO LDS kernels need no leaf records (DevScene::bvh_solo).
@@ -565,6 +707,7 @@ int commit_scene(Scene* s, int world) {
                 g.begin = (int)before;
                 for (const LeafTmp* L : ls) {
                     if (L->chain != ch || L->type != type) continue;
+                    if (world && generic && is_gen[(size_t)(L - f.leaves.data())]) continue;   // in the tree
                     if (world) {
                         LeafInfo li{};
                         li.type = type; li.chain = ch; li.mat = s->objs[L->obj].mat; li.flip = L->flip;
@@ -756,6 +899,40 @@ int commit_scene(Scene* s, int world) {
         }
         if (int rc = upload(s->d_order, order, &d.order)) return rc;
         d.n_order = (int32_t)order.size();
+        if (generic) {                               // leaf ids of the tree leaves, and every leaf's list position
+            std::vector<int32_t> gleaf, pos(leaves.size(), 0);
+            gleaf.reserve(gsrc.size());
+            for (const auto& tl : gsrc) gleaf.push_back(base[tl.first] + tl.second);
+            for (size_t k = 0; k < order.size(); ++k) pos[(size_t)order[k]] = (int32_t)k;
+            if (int rc = upload(s->d_gleaf, gleaf, &d.gleaf)) return rc;
+            d.n_gleaf = (int32_t)gleaf.size();
+            if (int rc = upload(s->d_leaf_pos, pos, &d.leaf_pos)) return rc;
+            if (int rc = upload(s->d_rot, rot, &d.rot)) return rc;
+            d.n_rot = (int32_t)rot.size();
+            if (!g0bvh2.empty() || !g0bleaf.empty()) {
+                if (int rc = upload(s->d_g0bvh2, g0bvh2, &d.g0bvh2)) return rc;
+                if (int rc = upload(s->d_g0bleaf, g0bleaf, &d.g0bleaf)) return rc;
+                d.g0bvh2_root = g0bvh2_root;
+                d.n_g0bvh2 = (int32_t)g0bvh2.size();
+            }
+        }
+    }
+    {   // rt_get_tree_info
+        rt_tree_info& ti = s->tree;
+        std::memset(&ti, 0, sizeof ti);
+        if (use_bvh) {
+            for (const PrimRef& r : refs) {
+                const bool world = f.leaves[(size_t)r.leaf].chain == -1;
+                if (r.type == LEAF_BEZIER) ++ti.curve_leaves;
+                else if (world && (r.type == LEAF_SPHERE || r.type == LEAF_MSPHERE)) ++ti.sphere_leaves;
+                else ++ti.generic_leaves;
+            }
+            ti.nodes = (int32_t)bvh2.size(); ti.depth = depth_all;
+            ti.nodes0 = (int32_t)(generic ? g0bvh2.size() : fbvh2.size()); ti.depth0 = depth0;
+        }
+        ti.group_leaves = (int32_t)leaves.size() - ti.sphere_leaves - ti.curve_leaves - ti.generic_leaves;
+        ti.rot_entries = generic ? (int32_t)rot.size() : 0;
+        ti.generic_min = (int32_t)gen_min;
     }
     if (int rc = upload(s->d_mats, s->mats, &d.mats)) return rc;
     if (int rc = upload(s->d_texs, s->texs, &d.texs)) return rc;

@@ -29,7 +29,9 @@ enum LeafType : int32_t { LEAF_SPHERE = 0, LEAF_MSPHERE = 1, LEAF_RECT_XY = 2, L
 constexpr int kLeafTypes = 8;
 constexpr int32_t GROUP_BVH = 8;               // group type: BVH over world-level spheres / curves
 // closest-hit kernel variants: scene features compiled in (extra = constant media, Klein limit sets)
-constexpr int kFeatCurves = 1, kFeatExtra = 2;
+// kFeatGeneric: the world tree holds generic leaves (rects, instanced spheres: DevScene::gleaf); such scenes
+// have no curves, media or Klein sets, so the bit is never combined with the other two
+constexpr int kFeatCurves = 1, kFeatExtra = 2, kFeatGeneric = 4;
 enum ChainOp : int32_t { OP_TRANSLATE = 0, OP_ROTATE_Y = 1 };
 
 struct DevTexture {            // texture.scm:12-50
@@ -75,7 +77,8 @@ struct MediumRec { int32_t bg_begin, bg_end, pad0, pad1; double neg_inv_density,
 // rz0, lx1, rx1, ly1, ry1, lz1, rz1}: the kernel tests both children with
 // packed f32 FMAs (v_pk_fma_f32) on adjacent register pairs.
 struct alignas(64) BvhNode2 { float b[12]; int32_t l, r, pad0, pad1; };
-struct BvhLeaf { int32_t sb, sn, mb, mn, bb, bn, pad0, pad1; };   // sphere / moving / curve ranges
+// sphere / moving / curve ranges; gb, gn: a range of DevScene::gleaf (generic tree leaves, else 0, 0)
+struct BvhLeaf { int32_t sb, sn, mb, mn, bb, bn, gb, gn; };
 // Trees that hold curves: a leaf holding exactly one curve k (and nothing
 // else) is referenced as ~(kDirectCurve + k), so a walk queues the curve from
 // the child ref itself instead of fetching a BvhLeaf record.
@@ -107,6 +110,11 @@ struct alignas(16) LeafInfo {
 
 struct ChainOpRec { int32_t op, pad; double x, y, z; };   // translate: (x,y,z); rotate: x=sin, y=cos
 struct Chain { int32_t n, pad; ChainOpRec ops[kMaxChain]; };
+
+// One rotation sequence of an instance chain (its rotate-y ops in chain_ray's order; n = 0: none) and
+// the local axes (bit 0 x, 1 y, 2 z) that planes of tree rects under it are normal to (DevScene::rot)
+constexpr int kMaxRot = 16;                    // table entries; rects under further rotations stay in groups
+struct RotEntry { int32_t n, axes; double sc[kMaxChain][2]; };   // (sin, cos) per op
 
 // One group = leaves [begin, end) of one type under one chain (-1 = world).
 struct Group { int32_t type, chain, begin, end; };   // begin/end index the type array
@@ -199,6 +207,18 @@ struct DevScene {
     // texel (R | G << 8 | B << 16), so a lookup is one load; has_image_tex selects the kernels' kTexImage instances
     int32_t has_image_tex;                     // some texture is an image
     const uint32_t* teximg;
+    // Generic tree leaves (kFeatGeneric; n_gleaf = 0: none, everything below unused).  The world tree
+    // (bvh2 / bleaf) then holds the world-level spheres and moving spheres, the instanced ones and the
+    // rects, every leaf as a range of gleaf = leaf ids (BvhLeaf::gb, gn), tested one by one as
+    // list_closest tests them.  g0bvh2 / g0bleaf: the same leaves with every moving sphere bounded at
+    // time 0 only (nullptr: no moving spheres, the one tree serves every ray).  leaf_pos: leaf id ->
+    // position in the flattened list, which decides between hits at one t (tie_take).  rot: the
+    // rotation sequences of the tree rects' chains with the local axes their planes are normal to; a
+    // ray whose local direction is exactly zero on such an axis takes list_closest (order_dependent).
+    const int32_t* gleaf;  int32_t n_gleaf;
+    const int32_t* leaf_pos;
+    const BvhNode2* g0bvh2; const BvhLeaf* g0bleaf; int32_t g0bvh2_root, n_g0bvh2;
+    const struct RotEntry* rot; int32_t n_rot;
 };
 
 // Wavefront path state, SoA, one slot per live path (ping-pong buffers).

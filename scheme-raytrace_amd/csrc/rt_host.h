@@ -169,6 +169,8 @@ struct Scene {
     DevBuf d_leaf_cls;
     DevBuf d_order;
     DevBuf d_teximg;                               // the image textures' texels
+    DevBuf d_gleaf, d_leaf_pos, d_g0bvh2, d_g0bleaf, d_rot;   // generic tree leaves (DevScene::gleaf)
+    rt_tree_info tree{};                           // rt_get_tree_info's record, filled by commit_scene
     size_t ext_lds = 0;                            // k_extend_lds: LDS bytes (0 = not used) and grid cap
     uint32_t ext_lds_blocks = 0;
     size_t cam_lds = 0;                            // k_camera (fused raygen + depth-0 extend), same

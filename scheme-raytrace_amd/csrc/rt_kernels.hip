@@ -26,7 +26,9 @@
 //
 // F selects the closest-hit features compiled in (kFeatCurves: curve batching
 // state; kFeatExtra: constant media and Klein limit sets, which draw random
-// numbers / march inside the hit test), so sphere scenes run lean kernels.
+// numbers / march inside the hit test; kFeatGeneric, on its own: a world tree
+// of rects and instanced spheres, bvh_closest_generic), so sphere scenes run
+// lean kernels.
 //
 // All arithmetic is f64 like the reference's flonums.  Random numbers come
 // from a Philox4x32-10 stream keyed by (seed, pixel, sample) with a per-path
@@ -1510,6 +1512,138 @@ __device__ __forceinline__ Tree0 tree0_hbm(const DevScene& sc) { return Tree0{sc
 struct TreeA { const BvhNode2* nodes; const BvhLeaf* leaves; const SphereRec* sph; const MSphereRec* msph; };
 __device__ __forceinline__ TreeA treeA_hbm(const DevScene& sc) { return TreeA{sc.bvh2, sc.bleaf, sc.sph, sc.msph}; }
 
+// ------------------------------------------------- generic tree leaves
+// Scenes whose world tree holds rects and instanced spheres (kFeatGeneric, DevScene::gleaf).  The tree
+// meets the leaves in its own order, so hits at one t are decided as the list decides them.  Scanning in
+// list order a sphere takes the hit only with t < closest and a rect unless t > closest: of the elements
+// at the smallest t the last rect wins, and the first sphere when none of them is a rect.  tie_take: does
+// leaf `id` (a rect or not) at t == closest take the hit from `best`?  Only reached on exact ties.
+__device__ __noinline__ bool tie_take(const DevScene& sc, const int32_t best, const int32_t id, const bool rect) {
+    if (best < 0) return rect;                             // closest is still t-max: only a rect passes t <= closest
+    const int32_t bt = sc.leaves[best].type;
+    const bool brect = bt >= LEAF_RECT_XY && bt <= LEAF_RECT_YZ;
+    if (rect) return !brect || sc.leaf_pos[id] > sc.leaf_pos[best];
+    return !brect && sc.leaf_pos[id] < sc.leaf_pos[best];
+}
+// sphere_test with ties by list position.  The root a sphere reports does not depend on closest (the
+// nearer one if it is beyond t-min, else the farther), so the tie is tested on that root.
+__device__ __forceinline__ void sphere_test_tie(const DevScene& sc, const v3 o, const v3 d, const double a,
+                                                const double ia, const v3 c, const double rr, const int32_t id,
+                                                double& closest, int32_t& best) {
+    const v3 oc = o - c;
+    const double b = dot(oc, d);
+    const double cc = dot(oc, oc) - rr;
+    const double disc = b * b - a * cc;
+    if (disc > 0.0) {
+        const double sq = sqrt(disc);
+        double t = div_ia(-b - sq, a, ia);
+        if (!(kTmin < t && t <= closest)) t = div_ia(-b + sq, a, ia);
+        if (kTmin < t && (t < closest || (t == closest && tie_take(sc, best, id, false)))) { closest = t; best = id; }
+    }
+}
+// Rays whose closest hit may depend on the list's order through a tree rect (Q20): the rect's t is NaN
+// (0/0, or from a non-finite ray) and passes every comparison, but a slab test may cull the rect before
+// it is seen.  Conservative: any ray with a component that is not finite and moderate, or whose direction
+// in the frame of some tree rect is exactly zero along that rect's normal (DevScene::rot: one entry per
+// distinct rotation sequence).  Such rays take list_closest.
+__device__ __forceinline__ bool order_dependent(const DevScene& sc, const v3 o, const v3 d) {
+    const double lim = 1e150;
+    if (!(fabs(o.x) < lim && fabs(o.y) < lim && fabs(o.z) < lim && fabs(d.x) < lim && fabs(d.y) < lim && fabs(d.z) < lim))
+        return true;
+    bool dep = false;
+    for (int e = 0; e < sc.n_rot; ++e) {
+        const RotEntry& R = sc.rot[e];
+        double x = d.x, z = d.z;
+        for (int k = 0; k < R.n; ++k) {                     // chain_ray's rotation of the direction
+            const double sn = R.sc[k][0], cs = R.sc[k][1];
+            const double nx = cs * x - sn * z, nz = sn * x + cs * z;
+            x = nx; z = nz;
+        }
+        dep = dep || ((R.axes & 1) && x == 0.0) || ((R.axes & 2) && d.y == 0.0) || ((R.axes & 4) && z == 0.0);
+    }
+    return dep;
+}
+// One leaf of the world's list against the shrinking closest: list_closest's per-leaf test (the same
+// operations on the same records, so the same t bit for bit), ties by list position.
+__device__ __forceinline__ void leaf_test_generic(const DevScene& sc, const int32_t id, const v3 o0, const v3 d0,
+                                                  const double time, double& closest, int32_t& best) {
+    const int4 L = *reinterpret_cast<const int4*>(&sc.leaves[id]);          // type, chain, local, flip
+    const int32_t type = L.x, s = L.z;
+    v3 o = o0, d = d0;
+    if (L.y >= 0) chain_ray(sc.chains[L.y], o, d);
+    if (type == LEAF_SPHERE) {
+        const double a = dot(d, d), ia = 1.0 / a;
+        const SphereRec S = sc.sph[s];
+        sphere_test_tie(sc, o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, id, closest, best);
+    } else if (type == LEAF_MSPHERE) {
+        const double a = dot(d, d), ia = 1.0 / a;
+        const MSphereRec S = sc.msph[s];
+        const double frac = (time - S.t0) / S.den;
+        const v3 cen = mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * frac;
+        sphere_test_tie(sc, o, d, a, ia, cen, S.rr, id, closest, best);
+    } else {
+        double ok, dk, oa, da, ob, db;
+        if (type == LEAF_RECT_XY) { ok = o.z; dk = d.z; oa = o.x; da = d.x; ob = o.y; db = d.y; }
+        else if (type == LEAF_RECT_XZ) { ok = o.y; dk = d.y; oa = o.x; da = d.x; ob = o.z; db = d.z; }
+        else { ok = o.x; dk = d.x; oa = o.y; da = d.y; ob = o.z; db = d.z; }
+        const RectRec R = sc.rect[s];
+        const double t = (R.k - ok) / dk;
+        if (t < kTmin || t > closest) return;
+        const double A = oa + t * da, Bv = ob + t * db;
+        if (A < R.a0 || A > R.a1 || Bv < R.b0 || Bv > R.b1) return;
+        if (t == closest && !tie_take(sc, best, id, true)) return;
+        closest = t; best = id;
+    }
+}
+// bvh_closest_lane's walk over a tree of generic leaves (nodes / leaves / root: the all-times tree or the
+// time-0 one): the same per-lane traversal, each leaf's gleaf range tested leaf by leaf.  Every loop is
+// bounded by the tree: a lane enters a node at most once, and a leaf's range lies inside gleaf.
+__device__ __forceinline__ void bvh_closest_generic(const DevScene& sc, const v3 o, const v3 d, const double time,
+                                                    double& closest, int32_t& best, uint32_t* lstk, const int lmax,
+                                                    const BvhNode2* __restrict__ nodes,
+                                                    const BvhLeaf* __restrict__ leaves, const int32_t root) {
+    constexpr int32_t kDone = INT32_MIN;
+    const BoxRay br = box_ray(o, d);
+    const uint32_t stride = blockDim.x;
+    uint32_t sp = 0;
+    const uint32_t slim = (uint32_t)lmax * stride;
+    int32_t node = root, pend = kDone;
+    float tcap = f32_up(closest);
+    while (node != kDone || pend != kDone) {
+        while (node != kDone) {
+            if (node < 0) {                                   // a leaf
+                if (pend != kDone) break;                     // one is already parked
+                pend = node;
+                node = sp ? (int32_t)lstk[sp -= stride] : kDone;
+            } else {
+                float tl, tr;
+                bool hl, hr;
+                const BvhNode2 M = nodes[node];
+                node_hit(M, br, tcap, hl, hr, tl, tr);
+                if (hl && hr) {
+                    const bool lfirst = tl <= tr;
+                    if (sp < slim) { lstk[sp] = (uint32_t)(lfirst ? M.r : M.l); sp += stride; }
+                    node = lfirst ? M.l : M.r;
+                } else if (hl) {
+                    node = M.l;
+                } else if (hr) {
+                    node = M.r;
+                } else {
+                    node = sp ? (int32_t)lstk[sp -= stride] : kDone;
+                }
+            }
+            if (__ballot(pend == kDone) == 0ull) break;       // every active lane has a leaf parked
+        }
+        if (pend != kDone) {
+            const BvhLeaf L = leaves[~pend];
+            const int gb = max(L.gb, 0), ge = min(L.gb + L.gn, sc.n_gleaf);
+            for (int g = gb; g < ge; ++g) leaf_test_generic(sc, sc.gleaf[g], o, d, time, closest, best);
+            pend = kDone;
+            tcap = f32_up(closest);
+        }
+    }
+}
+
 // One non-BVH group of hit-obj-list (geometry.scm:33-50): its primitives in
 // list order against the shrinking closest.
 template <int F>
@@ -1518,6 +1652,7 @@ __device__ __forceinline__ void group_closest(const DevScene& sc, const Group& G
                                               bool* nan_t = nullptr) {
     constexpr bool BEZ = (F & kFeatCurves) != 0;
     constexpr bool MED = (F & kFeatExtra) != 0;
+    constexpr bool GEN = (F & kFeatGeneric) != 0;      // the tree met leaves out of list order: ties by position
     v3 o = o0, d = d0;
     if (G.chain >= 0) chain_ray(sc.chains[G.chain], o, d);
     const int32_t base = sc.leaf_base[G.type];
@@ -1525,7 +1660,8 @@ __device__ __forceinline__ void group_closest(const DevScene& sc, const Group& G
         const double a = dot(d, d), ia = 1.0 / a;
         for (int s = G.begin; s < G.end; ++s) {
             const SphereRec S = sc.sph[s];
-            sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, base + s, closest, best);
+            if constexpr (GEN) sphere_test_tie(sc, o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, base + s, closest, best);
+            else sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, base + s, closest, best);
         }
     } else if (G.type == LEAF_MSPHERE) {               // geometry.scm:177-208
         const double a = dot(d, d), ia = 1.0 / a;
@@ -1538,7 +1674,8 @@ __device__ __forceinline__ void group_closest(const DevScene& sc, const Group& G
                 last_t0 = S.t0; last_den = S.den; have = true;
             }
             const v3 cen = mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * frac;
-            sphere_test(o, d, a, ia, cen, S.rr, base + s, closest, best);
+            if constexpr (GEN) sphere_test_tie(sc, o, d, a, ia, cen, S.rr, base + s, closest, best);
+            else sphere_test(o, d, a, ia, cen, S.rr, base + s, closest, best);
         }
     } else if (G.type == LEAF_KLEIN) {                 // geometry.scm:645-673
         if (MED) {
@@ -1576,6 +1713,7 @@ __device__ __forceinline__ void group_closest(const DevScene& sc, const Group& G
             if (t < kTmin || t > closest) continue;
             const double A = oa + t * da, Bv = ob + t * db;
             if (A < R.a0 || A > R.a1 || Bv < R.b0 || Bv > R.b1) continue;
+            if constexpr (GEN) { if (t == closest && !tie_take(sc, best, base + s, true)) continue; }
             closest = t; best = base + s;
         }
     }
@@ -1644,12 +1782,27 @@ __device__ __forceinline__ int32_t closest_hit(const DevScene& sc, const v3 o0, 
                                                const int lmax, BezWave* bw, Rng* rng, const Tree0 t0,
                                                const TreeA ta) {
     constexpr bool BEZ = (F & kFeatCurves) != 0;
+    constexpr bool GEN = (F & kFeatGeneric) != 0;
     int32_t best = -1;
     bool nan_t = false;
     closest = kTmax;
+    if constexpr (GEN) {
+        static_assert(sizeof(SE) == 4 && F == kFeatGeneric, "generic tree leaves: the HBM walk, no curves or media");
+        if (order_dependent(sc, o0, d0)) {                      // the list's order decides
+            list_closest<F>(sc, o0, d0, time, closest, best);
+            return best;
+        }
+    }
     for (int g = 0; g < sc.n_groups; ++g) {
         const Group G = sc.groups[g];
         if (G.type == GROUP_BVH) {
+            if constexpr (GEN) {
+                if (sc.g0bvh2 != nullptr && __double_as_longlong(time) == 0ll)
+                    bvh_closest_generic(sc, o0, d0, time, closest, best, lstk, lmax, sc.g0bvh2, sc.g0bleaf, sc.g0bvh2_root);
+                else
+                    bvh_closest_generic(sc, o0, d0, time, closest, best, lstk, lmax, sc.bvh2, sc.bleaf, sc.bvh2_root);
+                continue;
+            }
             if (BEZ && sc.bvh_has_bez)
                 bvh_closest_curves(sc, o0, d0, time, closest, best, reinterpret_cast<uint32_t*>(lstk), lmax, *bw);
             else if (sc.fbvh2 && (sc.tree0_any_time || __double_as_longlong(time) == 0ll))   // the time-0 tree
@@ -3256,6 +3409,7 @@ static bool finish_generic() {               // RTAMD_FINISH_GENERIC: the group-
     return e != nullptr && e[0] != '0';
 }
 static int scene_features(const DevScene& sc) {
+    if (sc.n_gleaf > 0) return kFeatGeneric;         // (commit_scene: never with curves, media or Klein sets)
     return (sc.n_bez > 0 ? kFeatCurves : 0) | (sc.n_med > 0 || sc.n_klein > 0 ? kFeatExtra : 0);
 }
 static int scene_tex_level(const DevScene& sc) {     // the instances a scene's launches take
@@ -3306,6 +3460,7 @@ using FinishKernel = void (*)(const DevScene*, RenderParams, PathState, QView, u
                               uint32_t);
 using FeaturesKernel = void (*)(DevScene, RenderParams, uint32_t, double*);
 static ExtendKernel extend_kernel(const DevScene& sc) {
+    if (scene_features(sc) == kFeatGeneric) return k_extend<kFeatGeneric>;
     return dispatch([](auto F) -> ExtendKernel { return k_extend<F()>; }, UpTo<3>{scene_features(sc)});
 }
 // FUSE: 0 one depth, 1 every depth from fuse->depth on with the device libm, 2 with the exact libm
@@ -3322,6 +3477,7 @@ static CameraKernel camera_kernel(const DevScene& sc) {
                   !sc.tree0_any_time, sc.bvh_solo != 0);
 }
 static HitRaysKernel hit_rays_kernel(const DevScene& sc) {
+    if (scene_features(sc) == kFeatGeneric) return k_hit_rays<kFeatGeneric>;
     return scene_features(sc) ? k_hit_rays<kFeatCurves | kFeatExtra> : k_hit_rays<0>;
 }
 // the probe of k_extend_lds's walk (time0) or k_camera's: the instance with that kernel's arguments
@@ -3358,6 +3514,10 @@ static int finish_tex_level(const DevScene& sc) {
 static FinishKernel finish_kernel(const DevScene& sc, const RenderParams& rp, const bool solo) {
     const int f = scene_features(sc), tl = finish_tex_level(sc);
     const bool ex = rp.exact_libm != 0;
+    if (f == kFeatGeneric)
+        return dispatch([](auto IMG, auto EX) -> FinishKernel {
+            return k_finish<kFeatGeneric, IMG() ? kTexImage : kTexPerlin, true, false, EX()>;
+        }, tl == kTexImage, ex);
     if (f > 0)
         return dispatch([](auto F1, auto IMG, auto EX) -> FinishKernel {
             return k_finish<F1() + 1, IMG() ? kTexImage : kTexPerlin, true, false, EX()>;
@@ -3366,6 +3526,8 @@ static FinishKernel finish_kernel(const DevScene& sc, const RenderParams& rp, co
                   TexLevel{tl}, sc.light.type != LIGHT_OFF, solo, ex);
 }
 static FeaturesKernel features_kernel(const DevScene& sc) {
+    if (scene_features(sc) == kFeatGeneric)
+        return dispatch([](auto TL) -> FeaturesKernel { return k_features<kFeatGeneric, TL()>; }, TexLevel{scene_tex_level(sc)});
     return dispatch([](auto F, auto TL) -> FeaturesKernel { return k_features<F(), TL()>; },
                   UpTo<3>{scene_features(sc)}, TexLevel{scene_tex_level(sc)});
 }

@@ -470,4 +470,12 @@ int rt_get_scene_info(int scene, rt_scene_info* out) {
     return 0;
 }
 
+int rt_get_tree_info(int scene, rt_tree_info* out) {
+    LOCK_SCENE(s, scene);
+    if (!out) return fail("null out pointer");
+    if (!s->committed) return fail("scene not committed (rt_scene_commit)");
+    *out = s->tree;
+    return 0;
+}
+
 }  // extern "C"

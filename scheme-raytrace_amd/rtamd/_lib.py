@@ -61,6 +61,13 @@ class RtSceneInfo(ctypes.Structure):
                 ("commit_threads", ctypes.c_int32), ("tree0_any_time", ctypes.c_int32)]
 
 
+class RtTreeInfo(ctypes.Structure):
+    """rt_tree_info (RT_HAS_GENERIC_BVH): which leaves the world tree took."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("sphere_leaves", "curve_leaves", "generic_leaves", "group_leaves",
+                                              "nodes", "depth", "nodes0", "depth0", "rot_entries",
+                                              "generic_min")] + [("reserved", ctypes.c_int32 * 6)]
+
+
 class RtAdaptive(ctypes.Structure):
     """rt_adaptive: the adaptive render's rounds (min / max / batch passes) and stop rule (tol, floor)."""
     _fields_ = [("min_spp", ctypes.c_uint32), ("max_spp", ctypes.c_uint32), ("batch_spp", ctypes.c_uint32),
@@ -145,6 +152,7 @@ _SIGNATURES = {
     "rt_get_stats": [ctypes.c_int, ctypes.POINTER(RtStats)],
     "rt_set_profiling": [ctypes.c_int, ctypes.c_int],
     "rt_get_scene_info": [ctypes.c_int, ctypes.POINTER(RtSceneInfo)],
+    "rt_get_tree_info": [ctypes.c_int, ctypes.POINTER(RtTreeInfo)],                          # RT_HAS_GENERIC_BVH
     "rt_resolve_u8": [_c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_u8_p],
     "rt_shard_pixels": [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32),
                         ctypes.POINTER(ctypes.c_int64)],

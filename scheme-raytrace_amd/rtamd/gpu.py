@@ -210,6 +210,15 @@ def scene_info(scene_handle):
     return {name: getattr(s, name) for name, _ in s._fields_ if name != "reserved"}
 
 
+def tree_info(scene_handle):
+    """rt_get_tree_info as a dict: the leaves the world tree took (world-level spheres, curves, generic
+    leaves), those left in brute-force groups, the trees' sizes, the rotation table's entries and the
+    RTAMD_BVH_GENERIC_MIN in force at the commit."""
+    s = _lib.RtTreeInfo()
+    call("rt_get_tree_info", scene_handle, ctypes.byref(s))
+    return {name: getattr(s, name) for name, _ in s._fields_ if name != "reserved"}
+
+
 def render_host(scene, nx, ny, spp_begin, spp_count, seed, accum, ctx=None):
     """rt_render: accum is a host float64 array of nx*ny*3 (updated in place)."""
     h = upload(scene, ctx)

@@ -345,7 +345,63 @@ def cornell_curves_small(nx, ny):
     return cornell_curves(nx, ny, n_curves=4096, width=3.0)
 
 
+NEXT_WEEK_SEED = 0x5EED0007
+
+
+def next_week(nx, ny, seed=NEXT_WEEK_SEED, perlin_seed=PERLIN_SEED, boxes_per_side=20, cluster=1000, earth=True):
+    """The closing scene of "Ray Tracing: The Next Week", written with the reference's constructors: a field
+    of boxes_per_side^2 ground boxes of seeded random heights under make-bvh-node, the ceiling light, a moving
+    sphere, a glass and a metal sphere, a second glass sphere (the book's medium boundary), an image-textured
+    and a marble sphere, and `cluster` small spheres, each under translate o rotate-y, in one make-bvh-node
+    (the book puts the two transforms around the node; the reference's rotate-y and translate take the hit's
+    material from the object they wrap, geometry.scm:537, which a bvh node does not have — wrapped sphere by
+    sphere the reference can express the scene, and the library flattens both forms to the same leaves under
+    one instance chain).  The book's
+    two constant media (the blue volume inside the second glass sphere and the thin mist around everything)
+    are left out: a medium's hit test draws random numbers in list order, and scenes with one keep the
+    brute-force groups (include/rt.h, rt_add_bvh).  Black sky, shutter [0, 1].  earth=False: the globe takes a
+    checker texture instead of its image (the oracle restates no image textures)."""
+    import numpy as np
+
+    rr = HostStream(seed)
+    ground = g.make_lambertian(g.constant_texture(v.vec3(0.48, 0.83, 0.53)))
+    white = g.make_lambertian(g.constant_texture(v.vec3(0.73, 0.73, 0.73)))
+    light = g.make_diffuse_light(g.constant_texture(v.vec3(7, 7, 7)))
+    w = 2000.0 / boxes_per_side
+    boxes = []
+    for i in range(boxes_per_side):
+        for j in range(boxes_per_side):
+            x0, z0 = -1000 + i * w, -1000 + j * w
+            boxes.append(g.make_box(v.vec3(x0, 0, z0), v.vec3(x0 + w, 100 * (rr() + 0.01), z0 + w), ground))
+    ey, ex = np.mgrid[0:32, 0:64]
+    img = np.zeros((32, 64, 3), dtype=np.uint8)               # a banded globe: sea, land patches, ice caps
+    land = ((ex // 8 + ey // 6) % 3 == 0) & (ey > 3) & (ey < 28)
+    img[..., 0] = np.where(land, 60 + 2 * ex, 20)
+    img[..., 1] = np.where(land, 140, 60 + 2 * ey)
+    img[..., 2] = np.where(land, 50, 170)
+    img[(ey <= 3) | (ey >= 28)] = 235
+    globe = g.make_image_texture(img, 64, 32) if earth else g.checker_texture(
+        g.constant_texture(v.vec3(0.1, 0.3, 0.7)), g.constant_texture(v.vec3(0.3, 0.6, 0.2)))
+    small = [g.translate(g.rotate_y(g.make_sphere(v.vec3(165 * rr(), 165 * rr(), 165 * rr()), 10, white), 15),
+                         v.vec3(-100, 270, 395)) for _ in range(cluster)]
+    objs = [
+        g.make_bvh_node(boxes, 0, 1),
+        g.flip_normals(g.make_xz_rect(123, 423, 147, 412, 554, light)),   # (lights emit from their front)
+        g.make_moving_sphere(v.vec3(400, 400, 200), v.vec3(430, 400, 200), 0, 1, 50,
+                             g.make_lambertian(g.constant_texture(v.vec3(0.7, 0.3, 0.1)))),
+        g.make_sphere(v.vec3(260, 150, 45), 50, g.make_dielectric(1.5)),
+        g.make_sphere(v.vec3(0, 150, 145), 50, g.make_metal(g.constant_texture(v.vec3(0.8, 0.8, 0.9)), 1.0)),
+        g.make_sphere(v.vec3(360, 150, 145), 70, g.make_dielectric(1.5)),
+        g.make_sphere(v.vec3(400, 200, 400), 100, g.make_lambertian(globe)),
+        g.make_sphere(v.vec3(220, 280, 300), 80, g.make_lambertian(g.marble_texture(0.1))),
+        g.make_bvh_node(small, 0, 1),
+    ]
+    cam = make_camera(v.vec3(478, 278, -600), v.vec3(278, 278, 0), v.vec3(0, 1, 0), 40, nx / ny, 0, 10, 0, 1)
+    return g.make_scene(objs, cam, g.black, perlin=_perlin.from_seed(perlin_seed))
+
+
 SCENES = {
+    "next_week": next_week,
     "cover": random_scene,
     "cover_marble": marble_random_scene,
     "test_scene": test_scene,
