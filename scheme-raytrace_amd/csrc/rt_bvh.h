@@ -1,4 +1,4 @@
-// rt_bvh.h — host-side BVH construction for commit_scene (rt_commit.cpp): SAH build over the world-level
+// rt_bvh.h — host-side BVH construction for build_scene (rt_build.cpp): SAH build over the world-level
 // spheres, moving spheres and curves, the BVH2 traversal layout and the BVH4 collapse for the curve walk.
 // Host code only (no device code, no HIP): tests/csrc/bvh_check.cpp compiles it with g++ to check the
 // threaded build against the serial one.

@@ -1,8 +1,9 @@
 // rt_host.h — what librtamd's host translation units share: the object model behind the handles of
-// include/rt.h, the handle registry, error reporting, the entry points' common prologues and the
-// functions the units call in each other.
+// include/rt.h (rt_model.h) with its device side, the handle registry, error reporting, the entry
+// points' common prologues and the functions the units call in each other.
 //   rt_scene.cpp     contexts, options, the scene builder, statistics
-//   rt_commit.cpp    flattening, BVH build, upload (commit_scene)
+//   rt_build.cpp     the host scene of a commit: flattening, BVH builds, records (build_scene; no HIP)
+//   rt_commit.cpp    its upload and the device-dependent sizing (commit_scene)
 //   rt_render.cpp    the render scheduler (render_impl) and the render / probe / resolve entry points
 //   rt_gather.cpp    the frame-end gather (RCCL and in-process)
 //   rt_adaptive.cpp  adaptive sampling
@@ -21,6 +22,7 @@
 
 #include "../../include/rt.h"
 #include "rt_device.h"
+#include "rt_model.h"
 
 namespace rtamd {
 
@@ -33,21 +35,6 @@ int fail(const std::string& msg);
         if (e_ != hipSuccess)                                                          \
             return fail(std::string(#expr) + ": " + hipGetErrorString(e_));            \
     } while (0)
-
-// ------------------------------------------------------------- objects
-enum ObjType { O_SPHERE, O_MSPHERE, O_RECT, O_FLIP, O_BOX, O_TRANSLATE, O_ROTATE_Y, O_LIST, O_BVH, O_BEZIER, O_MEDIUM, O_KLEIN };
-
-struct Obj {
-    ObjType type;
-    int mat = -1, child = -1, axis = 0;
-    std::vector<int> kids;
-    double c0[3] = {0, 0, 0}, c1[3] = {0, 0, 0};
-    double r = 0, t0 = 0, t1 = 0;
-    double a0 = 0, a1 = 0, b0 = 0, b1 = 0, k = 0;
-    double sin_t = 0, cos_t = 1;
-    double cp[12] = {0};       // O_BEZIER control points a, b, c, d
-    double width = 0;
-};
 
 struct DevBuf {
     void* p = nullptr;
@@ -145,19 +132,8 @@ struct Context {
     DevBuf dn_signal[2], dn_guide;
 };
 
-struct Scene {
+struct Scene : SceneDesc {       // the builder's record (rt_model.h) and what a commit made of it
     int ctx = -1;
-    std::vector<DevTexture> texs;
-    std::vector<uint32_t> teximg;     // the image textures' texels (rt_add_texture_image), as DevScene::teximg
-    std::vector<DevMaterial> mats;
-    std::vector<Obj> objs;
-    double cam[RT_CAMERA_DOUBLES] = {0};
-    bool have_cam = false;
-    int sky = RT_SKY_GRADIENT;
-    int light = -1;                   // rt_set_light_sampling target (-1: off)
-    std::vector<double> ranvec;
-    std::vector<int32_t> perm;
-    bool have_perlin = false;
     bool committed = false;
 
     // flattened + uploaded
@@ -245,7 +221,7 @@ inline int check_frame(int nx, int ny) {
 }
 
 // ------------------------------------------------------------- between units
-// rt_commit.cpp: flatten the object tree under `world`, build its BVHs, upload the device scene
+// rt_commit.cpp: build the host scene of the object tree under `world` (rt_build.h), upload it
 int commit_scene(Scene* s, int world);
 
 // The pixels a render covers: rows [y0, y1) of the frame (trace-all: every

@@ -1,4 +1,4 @@
-// rt_leafbox.h — world-space bounding boxes of flattened leaves for the world BVH (rt_commit.cpp): the
+// rt_leafbox.h — world-space bounding boxes of flattened leaves for the world BVH (rt_build.cpp): the
 // primitive's own box taken through its instance chain.  Host code only (no device code, no HIP):
 // tests/csrc/bvh_generic_check.cpp compiles it with g++.
 #pragma once

@@ -174,7 +174,7 @@ class Leaf:
 
 
 def flatten(scene):
-    """The scene's leaves in hit-obj-list order, as the library flattens them (rt_commit.cpp, Flattener)."""
+    """The scene's leaves in hit-obj-list order, as the library flattens them (rt_build.cpp, Flattener)."""
     out = []
 
     def walk(o, chain):

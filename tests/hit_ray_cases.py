@@ -24,9 +24,9 @@ of ray is built from the scene's own primitives, so that the edge is actually me
              every loop is bounded by the tree or list size, not by ray values)
 
 Ray times stay inside [min(t0, t1, 0), max(t0, t1, 0)] of the camera shutter: the all-times trees (the
-library's, rt_commit.cpp, and the oracle's, scene_prepare) bound a moving sphere over those times only,
+library's, rt_build.cpp, and the oracle's, scene_prepare) bound a moving sphere over those times only,
 so a ray of another time is outside what either tree is built for.  Origins of sphere scenes stay inside
-the radius the f32 box margin is sized for (scene_radius, rt_commit.cpp: 4 x the farthest primitive).
+the radius the f32 box margin is sized for (scene_radius, rt_build.cpp: 4 x the farthest primitive).
 """
 import numpy as np
 
@@ -152,7 +152,7 @@ ORACLE_TREE_CASES = {
 #: lies in the ceiling's plane (y = 5, dy = 0) and runs into the wall x = -6 at t = 6.  hit-obj-list meets the
 #: wall first, then the ceiling, whose t = 0/0 = NaN passes both comparisons and becomes the closest hit; no
 #: later object passes (t > NaN is false, but the floor's t is -inf and the back wall's bounds fail): (NaN,
-#: ceiling).  The library groups the world's leaves by type (rt_commit.cpp, emit_groups: xy, xz, then yz
+#: ceiling).  The library groups the world's leaves by type (rt_build.cpp, emit_groups: xy, xz, then yz
 #: rects), so it meets the ceiling before the wall, whose t = 6 then passes `t > NaN`: (6, wall).
 IN_PLANE_RAY = ((0.0, 5.0, 0.0, -1.0, 0.0, 0.0, 0.0), "ceiling")
 
