@@ -160,9 +160,15 @@ int rt_add_list(int scene, const int* objs, int n, int* out_obj);
  *   - with RT_HAS_GENERIC_BVH, also rects (box faces included) under any instance chain or none, and spheres
  *     and moving spheres under an instance chain, whose world-space box is finite — when the scene has at
  *     least RTAMD_BVH_GENERIC_MIN such leaves (environment, read at commit; default 48) and
- *     holds no curve, no constant medium (so no medium boundary) and no Klein set.  Scenes with any of those
- *     are committed exactly as without RT_HAS_GENERIC_BVH.  Rects under more than 16 distinct rotations: the
- *     rects of the 17th rotation on stay outside the tree.
+ *     holds no curve, no constant medium (so no medium boundary) and no Klein set.  Rects under more than 16
+ *     distinct rotations: the rects of the 17th rotation on stay outside the tree.
+ *   - with RT_HAS_MEDIA_BVH, a scene with constant media and no curve and no Klein set is a media forest
+ *      when some segment of its list (the leaves between two media, a medium closing its
+ *     segment) has at least RTAMD_BVH_GENERIC_MIN such leaves.  Each segment is then decided on its own by the
+ *     two rules above over its own counts and gets a tree of its own, the first 8 segments that qualify;
+ *     rt_tree_info.segments / segment_trees report it.  Medium boundaries stay outside every tree.
+ *     Every other scene with a curve, a medium or a Klein set is committed exactly as without
+ *     RT_HAS_GENERIC_BVH.
  * Every other leaf is tested one by one for every ray segment, grouped by instance chain and type
  * (rt_tree_info.group_leaves counts them).  Whatever the tree takes, the closest hit is hit-obj-list's
  * (geometry.scm:33-50) over the flattened list, ties at one t included. */
@@ -312,6 +318,14 @@ int rt_hit_rays(int scene, int n, const double* rays, double* out_t, int32_t* ou
 enum { RT_WALK_HBM = 0, RT_WALK_LDS_TIME0 = 1, RT_WALK_LDS_CAMERA = 2 };
 int rt_hit_rays_walk(int scene, int walk, int n, const double* rays, double* out_t, int32_t* out_mat);
 
+/* rt_hit_rays with the path's random stream (RT_HAS_MEDIA_BVH; a test probe): the same rays through the same
+ * closest hit in device memory, ray k drawing from the stream of (seed, pixel k, sample 0) from its first
+ * number on, as a render's paths do; out_draws[k] = how many random numbers the query consumed (a constant
+ * medium draws one whenever the closest hit so far leaves part of its span).  Accepts every scene rt_hit_rays
+ * accepts and scenes with constant media. */
+int rt_hit_rays_stream(int scene, const double* rays, int n, uint64_t seed, double* out_t, int32_t* out_mat,
+                       int32_t* out_draws);
+
 /* converge's subdivision depth (bezier.scm:179-193) as the curve kernels compute it (bez_maxd): for n
  * curves given in ray space (cps = n x 12 doubles, the control points after bezier-transform) and 8 eps
  * each (eps = width / 20), out_depth[i] = ceiling((log z) / (log 4)) with z = sqrt(2) n (n-1) l0 / (8 eps),
@@ -377,9 +391,12 @@ typedef struct rt_tree_info {
     int32_t  nodes0, depth0;  /* the time-0 tree (0, 0: none) */
     int32_t  rot_entries;     /* distinct rotations among the tree rects' chains (no rotation counts as one) */
     int32_t  generic_min;     /* RTAMD_BVH_GENERIC_MIN in force at the commit */
-    int32_t  reserved[6];
+    int32_t  segments;        /* media forests (RT_HAS_MEDIA_BVH): segments of the list, cut after each constant medium; else 0 */
+    int32_t  segment_trees;   /* ... and how many of them got a tree; the counts above are then sums / maxima over those trees */
+    int32_t  reserved[4];
 } rt_tree_info;
 #define RT_HAS_GENERIC_BVH 1
+#define RT_HAS_MEDIA_BVH 1
 int rt_get_tree_info(int scene, rt_tree_info* out);
 /* Record per-kernel HIP events during renders (adds a little host overhead). */
 int rt_set_profiling(int scene, int enabled);

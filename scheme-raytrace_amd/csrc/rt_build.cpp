@@ -159,6 +159,33 @@ struct TreePlan {
     std::vector<PrimRef> gen_ref;     // ... and its box
     bool gen(const size_t i) const { return generic && is_gen[i]; }
 };
+// Leaf i of the list as a generic tree leaf: its world-space box, and for a rect its chain's rotation entered
+// in rot.  False: not one (a world-level sphere, a box that is not finite, a rect past a full table).
+bool generic_ref(const SceneDesc& s, const Flattener& f, const size_t i, const double tlo, const double thi,
+                 std::vector<RotEntry>& rot, PrimRef& r) {
+    const LeafTmp& L = f.leaves[i];
+    if (!is_rect(L.type) && L.chain < 0) return false;
+    int n_ops = 0;
+    const ChainOpRec* ops = chain_ops(f, L.chain, n_ops);
+    r = PrimRef{};
+    if (!leaf_world_box(leaf_geom(L, s.objs[L.obj]), ops, n_ops, tlo, thi, r.lo, r.hi)) return false;
+    if (is_rect(L.type)) {
+        RotEntry e{};
+        for (int k = 0; k < n_ops; ++k)
+            if (ops[k].op == OP_ROTATE_Y) { e.sc[e.n][0] = ops[k].x; e.sc[e.n][1] = ops[k].y; ++e.n; }
+        size_t at = 0;
+        while (at < rot.size() && (rot[at].n != e.n || std::memcmp(rot[at].sc, e.sc, sizeof e.sc) != 0)) ++at;
+        if (at == rot.size()) {
+            if (rot.size() >= (size_t)kMaxRot) return false;       // the table is full: the rect keeps its group
+            rot.push_back(e);
+        }
+        rot[at].axes |= L.type == LEAF_RECT_YZ ? 1 : L.type == LEAF_RECT_XZ ? 2 : 4;   // the plane's normal
+    }
+    for (int k = 0; k < 3; ++k) r.c[k] = 0.5 * (r.lo[k] + r.hi[k]);
+    r.leaf = (int)i;
+    r.type = L.type;
+    return true;
+}
 TreePlan choose_tree_leaves(const SceneDesc& s, const Flattener& f, const std::vector<int>& seg, const int nseg,
                             const BuildOptions& opt, std::vector<RotEntry>& rot) {
     TreePlan p;
@@ -175,28 +202,7 @@ TreePlan choose_tree_leaves(const SceneDesc& s, const Flattener& f, const std::v
         p.gen_ref.resize(f.leaves.size());
         p.is_gen.assign(f.leaves.size(), 0);
         for (size_t i = 0; i < f.leaves.size(); ++i) {
-            const LeafTmp& L = f.leaves[i];
-            if (!is_rect(L.type) && L.chain < 0) continue;
-            int n_ops = 0;
-            const ChainOpRec* ops = chain_ops(f, L.chain, n_ops);
-            PrimRef r{};
-            if (!leaf_world_box(leaf_geom(L, s.objs[L.obj]), ops, n_ops, tlo, thi, r.lo, r.hi)) continue;
-            if (is_rect(L.type)) {
-                RotEntry e{};
-                for (int k = 0; k < n_ops; ++k)
-                    if (ops[k].op == OP_ROTATE_Y) { e.sc[e.n][0] = ops[k].x; e.sc[e.n][1] = ops[k].y; ++e.n; }
-                size_t at = 0;
-                while (at < rot.size() && (rot[at].n != e.n || std::memcmp(rot[at].sc, e.sc, sizeof e.sc) != 0)) ++at;
-                if (at == rot.size()) {
-                    if (rot.size() >= (size_t)kMaxRot) continue;       // the table is full: the rect keeps its group
-                    rot.push_back(e);
-                }
-                rot[at].axes |= L.type == LEAF_RECT_YZ ? 1 : L.type == LEAF_RECT_XZ ? 2 : 4;   // the plane's normal
-            }
-            for (int k = 0; k < 3; ++k) r.c[k] = 0.5 * (r.lo[k] + r.hi[k]);
-            r.leaf = (int)i;
-            r.type = L.type;
-            p.gen_ref[i] = r;
+            if (!generic_ref(s, f, i, tlo, thi, rot, p.gen_ref[i])) continue;
             p.is_gen[i] = 1;
             ++n_gen;
         }
@@ -206,6 +212,58 @@ TreePlan choose_tree_leaves(const SceneDesc& s, const Flattener& f, const std::v
     p.in_tree.clear();
     for (size_t i = 0; i < f.leaves.size(); ++i)
         if (p.is_gen[i] || world_sphere(f.leaves[i])) p.in_tree.push_back((int)i);
+    return p;
+}
+
+// Media forests (include/rt.h, rt_add_bvh).  A scene with a constant medium, no curve and no
+// Klein set, in which some segment has at least opt.generic_min generic leaves: every segment is decided on
+// its own by choose_tree_leaves' rule over that segment's counts, and each tree it gets is a generic one
+// (also one of world-level spheres only: one walk).  The first kMaxSegTrees segments that qualify get
+// trees; rot holds the rotations of all the trees' rects.  on = false: the scene commits as without forests.
+constexpr int kMaxSegTrees = 8;
+struct ForestPlan {
+    bool on = false;
+    std::vector<std::vector<int>> tree;   // per segment: the list positions its tree takes, in list order
+    TreePlan leaves;                      // is_gen: by list position, in some tree; gen_ref: the generic leaves' boxes
+};
+ForestPlan choose_forest(const SceneDesc& s, const Flattener& f, const std::vector<int>& seg, const int nseg,
+                         const BuildOptions& opt, std::vector<RotEntry>& rot) {
+    ForestPlan p;
+    if (f.bounds.empty()) return p;
+    for (const LeafTmp& L : f.leaves)
+        if (L.type == LEAF_BEZIER || L.type == LEAF_KLEIN) return p;
+    const size_t n = f.leaves.size();
+    const double tlo = std::min(std::min(s.cam[22], s.cam[23]), 0.0), thi = std::max(std::max(s.cam[22], s.cam[23]), 0.0);
+    p.tree.resize((size_t)nseg);
+    p.leaves.is_gen.assign(n, 0);
+    p.leaves.gen_ref.resize(n);
+    std::vector<RotEntry> table;
+    int trees = 0;
+    size_t i = 0;
+    for (int sg = 0; sg < nseg && trees < kMaxSegTrees; ++sg) {
+        const size_t b = i;
+        while (i < n && seg[i] == sg) ++i;                     // [b, i): the segment's leaves, its medium last
+        std::vector<RotEntry> with = table;                    // the table with this segment's rects
+        std::vector<char> gen(i - b, 0);
+        size_t n_gen = 0, n_world = 0;
+        for (size_t j = b; j < i; ++j) {
+            const LeafTmp& L = f.leaves[j];
+            if (L.type == LEAF_MEDIUM) continue;
+            if (world_sphere(L)) { ++n_world; continue; }
+            gen[j - b] = generic_ref(s, f, j, tlo, thi, with, p.leaves.gen_ref[j]) ? 1 : 0;
+            n_gen += (size_t)gen[j - b];
+        }
+        const bool take_gen = n_gen > 0 && n_gen >= opt.generic_min && n_world + n_gen >= opt.bvh_min;
+        const bool take_world = n_world > 0 && n_world + (take_gen ? n_gen : 0) >= opt.bvh_min;
+        if (take_gen) { table.swap(with); p.on = true; }
+        for (size_t j = b; j < i; ++j)
+            if ((take_gen && gen[j - b]) || (take_world && world_sphere(f.leaves[j]))) {
+                p.tree[(size_t)sg].push_back((int)j);
+                p.leaves.is_gen[j] = 1;
+            }
+        trees += p.tree[(size_t)sg].empty() ? 0 : 1;
+    }
+    if (p.on) { rot.swap(table); p.leaves.generic = true; }
     return p;
 }
 
@@ -455,36 +513,119 @@ void emit_groups(const SceneDesc& s, const std::vector<LeafTmp>& src, const std:
     }
 }
 
-// Segment by segment: the groups of its leaves, then its medium with the medium's boundary groups
+// Segment sg: the groups of its leaves, then its medium with the medium's boundary groups.  listed: the
+// medium gets a list position of its own (media forests: DevScene::order holds it)
+void segment_one(const SceneDesc& s, const std::vector<int>& seg, const int sg, const bool skip_tree, const bool listed,
+                 const TreePlan& plan, HostScene& h) {
+    const Flattener& f = h.f;
+    std::vector<int> ls;
+    const LeafTmp* medium = nullptr;
+    for (size_t i = 0; i < f.leaves.size(); ++i) {
+        if (seg[i] != sg) continue;
+        if (f.leaves[i].type == LEAF_MEDIUM) medium = &f.leaves[i];
+        else ls.push_back((int)i);
+    }
+    emit_groups(s, f.leaves, ls, true, skip_tree, plan, h, h.groups);
+    COMMIT_MARK("emit");
+    if (!medium) return;
+    const Obj& o = s.objs[medium->obj];
+    const std::vector<LeafTmp>& bound = f.bounds[medium->aux];
+    std::vector<int> all(bound.size());
+    for (size_t k = 0; k < all.size(); ++k) all[k] = (int)k;
+    MediumRec m{};
+    m.bg_begin = (int)h.bgroups.size();
+    emit_groups(s, bound, all, false, false, plan, h, h.bgroups);
+    m.bg_end = (int)h.bgroups.size();
+    m.neg_inv_density = -(1 / o.r);             // (- (/ 1 density)), geometry.scm:564
+    LeafInfo li = leaf_info(*medium, o);
+    li.local = (int)h.med.size();
+    if (listed) {
+        const size_t pos = (size_t)(medium - f.leaves.data());
+        h.ll.ord_type[pos] = LEAF_MEDIUM;
+        h.ll.ord_local[pos] = li.local;
+    }
+    h.groups.push_back(Group{LEAF_MEDIUM, medium->chain, (int)h.med.size(), (int)h.med.size() + 1});
+    h.med.push_back(m);
+    h.ll.med.push_back(li);
+}
 void segment_records(const SceneDesc& s, const std::vector<int>& seg, const int nseg, const bool use_tree,
                      const TreePlan& plan, HostScene& h) {
+    for (int sg = 0; sg < nseg; ++sg) segment_one(s, seg, sg, use_tree && sg == 0, false, plan, h);
+}
+
+// A media forest's trees and records, segment by segment: [its tree] [its groups] [its medium].  Every tree is
+// appended to bvh2 / bleaf (flatten_bvh2's refs are absolute) with its leaves as ranges of gleaf, a time-0
+// twin of a tree that holds a moving sphere to g0bvh2 / g0bleaf; the tree's GROUP_BVH group carries the
+// roots (Group::begin, end).  h.refs: all trees' leaves, tree after tree.
+void forest_records(const SceneDesc& s, const BuildOptions& opt, const std::vector<int>& seg, const int nseg,
+                    const ForestPlan& fp, HostScene& h, Src& gsrc) {
     const Flattener& f = h.f;
+    DevScene& d = h.d;
+    const double tlo = std::min(std::min(s.cam[22], s.cam[23]), 0.0), thi = std::max(std::max(s.cam[22], s.cam[23]), 0.0);
+    const double margin = std::ldexp(scene_radius(s, f, opt.threads), -21);     // (world_tree: the f32 box margin)
+    d.bvh_pad = (float)margin;
+    h.threads = opt.threads;
+    h.tree.segments = nseg;
+    bool first = true;
     for (int sg = 0; sg < nseg; ++sg) {
-        std::vector<int> ls;
-        const LeafTmp* medium = nullptr;
-        for (size_t i = 0; i < f.leaves.size(); ++i) {
-            if (seg[i] != sg) continue;
-            if (f.leaves[i].type == LEAF_MEDIUM) medium = &f.leaves[i];
-            else ls.push_back((int)i);
+        const std::vector<int>& in = fp.tree[(size_t)sg];
+        if (!in.empty()) {
+            std::vector<PrimRef> refs(in.size());
+            for (size_t j = 0; j < in.size(); ++j) {
+                const size_t i = (size_t)in[j];
+                const LeafTmp& L = f.leaves[i];
+                if (!world_sphere(L)) { refs[j] = fp.leaves.gen_ref[i]; continue; }
+                PrimRef r{};                                  // (prim_boxes: a world-level sphere's box)
+                r.leaf = (int)i;
+                r.type = L.type;
+                leaf_local_box(leaf_geom(L, s.objs[L.obj]), tlo, thi, r.lo, r.hi);
+                pad_box(r.lo, r.hi);
+                for (int k = 0; k < 3; ++k) r.c[k] = 0.5 * (r.lo[k] + r.hi[k]);
+                refs[j] = r;
+            }
+            const std::vector<BvhNode> nodes = sah_build(refs, opt, false, h.sah_ms);
+            const int g0 = (int)gsrc.size();
+            int32_t root = 0, root0 = kNoTwin;
+            flatten_bvh2(nodes, margin, [&](int b, int e) { return BvhLeaf{0, 0, 0, 0, 0, 0, g0 + b, e - b}; },
+                         h.bvh2, h.bleaf, root, h.tree.depth, opt.threads);
+            bool moving = false;
+            for (const PrimRef& r : refs) {
+                const int local = grow(h, r.type);
+                put_record(s, f.leaves[(size_t)r.leaf], r.leaf, local, h);
+                gsrc.push_back({r.type, local});
+                moving = moving || r.type == LEAF_MSPHERE;
+            }
+            if (moving && !opt.no_bvh0) {                    // (time0_tree, generic form)
+                std::vector<PrimRef> refs0(refs);
+                for (size_t j = 0; j < refs0.size(); ++j) {
+                    PrimRef& r = refs0[j];
+                    const LeafTmp& L = f.leaves[(size_t)r.leaf];
+                    r.leaf = (int)j;                          // index into refs (-> gsrc)
+                    if (r.type != LEAF_MSPHERE) continue;
+                    int n_ops = 0;
+                    const ChainOpRec* ops = chain_ops(f, L.chain, n_ops);
+                    double lo[3], hi[3];
+                    if (!leaf_world_box(leaf_geom(L, s.objs[L.obj]), ops, n_ops, 0.0, 0.0, lo, hi)) continue;
+                    for (int k = 0; k < 3; ++k) { r.lo[k] = lo[k]; r.hi[k] = hi[k]; r.c[k] = 0.5 * (lo[k] + hi[k]); }
+                }
+                const std::vector<BvhNode> nodes0 = sah_build(refs0, opt, false, h.sah_ms);
+                const int g1 = (int)gsrc.size();
+                flatten_bvh2(nodes0, margin, [&](int b, int e) { return BvhLeaf{0, 0, 0, 0, 0, 0, g1 + b, e - b}; },
+                             h.g0bvh2, h.g0bleaf, root0, h.tree.depth0);
+                for (const PrimRef& r : refs0) gsrc.push_back(gsrc[(size_t)(g0 + r.leaf)]);
+                if (d.n_g0bvh2 == 0) d.g0bvh2_root = root0;
+                d.n_g0bvh2 = (int32_t)h.g0bvh2.size();
+            }
+            if (first) d.bvh2_root = root;
+            first = false;
+            h.groups.push_back(Group{GROUP_BVH, -1, root, root0});
+            h.refs.insert(h.refs.end(), refs.begin(), refs.end());
+            ++h.tree.segment_trees;
         }
-        emit_groups(s, f.leaves, ls, true, use_tree && sg == 0, plan, h, h.groups);
-        COMMIT_MARK("emit");
-        if (!medium) continue;
-        const Obj& o = s.objs[medium->obj];
-        const std::vector<LeafTmp>& bound = f.bounds[medium->aux];
-        std::vector<int> all(bound.size());
-        for (size_t k = 0; k < all.size(); ++k) all[k] = (int)k;
-        MediumRec m{};
-        m.bg_begin = (int)h.bgroups.size();
-        emit_groups(s, bound, all, false, false, plan, h, h.bgroups);
-        m.bg_end = (int)h.bgroups.size();
-        m.neg_inv_density = -(1 / o.r);             // (- (/ 1 density)), geometry.scm:564
-        LeafInfo li = leaf_info(*medium, o);
-        li.local = (int)h.med.size();
-        h.groups.push_back(Group{LEAF_MEDIUM, medium->chain, (int)h.med.size(), (int)h.med.size() + 1});
-        h.med.push_back(m);
-        h.ll.med.push_back(li);
+        segment_one(s, seg, sg, false, true, fp.leaves, h);
     }
+    d.lane_stack = std::max(h.tree.depth, h.tree.depth0);
+    COMMIT_MARK("forest");
 }
 
 // Leaf ids: spheres, moving spheres, then all rects (the three axis types share the rect array: leaf id =
@@ -556,18 +697,20 @@ void shade_fields(const SceneDesc& s, const int threads, HostScene& h) {
 }
 
 // The world's leaf ids in list order (list_closest; none for scenes with media, which keep the grouped
-// scan); the leaf ids of the tree entries (fid: of fsph's, gleaf: of the generic tree's) and every leaf's
+// scan, unless they are media forests: then the whole list, media included); the leaf ids of the tree entries (fid: of fsph's, gleaf: of the generic tree's) and every leaf's
 // list position
 int list_order(const bool generic, const Src& fsrc, const Src& gsrc, HostScene& h, std::string& err) {
     const int32_t* base = h.d.leaf_base;
     const LeafLists& ll = h.ll;
     if (!h.fbvh2.empty())
         for (const auto& sl : fsrc) h.fid.push_back(base[sl.first] + sl.second);
-    if (h.med.empty()) {
+    if (h.med.empty() || h.forest) {
         h.order.reserve(h.f.leaves.size());
         for (size_t i = 0; i < h.f.leaves.size(); ++i)
             if (ll.ord_type[i] >= 0) h.order.push_back(base[ll.ord_type[i]] + ll.ord_local[i]);
-        if (h.order.size() != h.leaves.size()) return fail_with(&err, "internal: list order and leaf records out of step");
+        // (a forest's media have boundary leaves, which are records outside the list)
+        if (h.order.size() != (h.forest ? h.f.leaves.size() : h.leaves.size()))
+            return fail_with(&err, "internal: list order and leaf records out of step");
     }
     h.d.n_order = (int32_t)h.order.size();
     if (!generic) return 0;
@@ -728,16 +871,20 @@ int build_scene(const SceneDesc& s, const int world, const BuildOptions& opt, Ho
     std::vector<int> seg;
     const int nseg = cut_segments(f, seg);
     COMMIT_MARK("flatten");
-    const TreePlan plan = choose_tree_leaves(s, f, seg, nseg, opt, h.rot);
+    const ForestPlan forest = choose_forest(s, f, seg, nseg, opt, h.rot);
+    h.forest = forest.on;
+    const TreePlan plan = forest.on ? forest.leaves : choose_tree_leaves(s, f, seg, nseg, opt, h.rot);
     h.generic = plan.generic;
-    h.refs = prim_boxes(s, f, plan, opt.threads);
+    if (!forest.on) h.refs = prim_boxes(s, f, plan, opt.threads);
     COMMIT_MARK("refs");
     h.ll.ord_type.assign(f.leaves.size(), -1);
     h.ll.ord_local.assign(f.leaves.size(), -1);
-    const bool use_tree = !h.refs.empty() && h.refs.size() >= opt.bvh_min;
+    const bool use_tree = forest.on || (!h.refs.empty() && h.refs.size() >= opt.bvh_min);
     bool tree0_direct = false;
     Src gsrc, fsrc;
-    if (use_tree) {
+    if (forest.on) {
+        forest_records(s, opt, seg, nseg, forest, h, gsrc);
+    } else if (use_tree) {
         Prefix pre;
         const double margin = world_tree(s, opt, plan.generic, h, pre);
         gsrc = tree_records(s, pre, plan.generic, opt.threads, h);
@@ -745,7 +892,7 @@ int build_scene(const SceneDesc& s, const int world, const BuildOptions& opt, Ho
             tree0_direct = time0_tree(s, opt, plan.generic, pre, margin, h, gsrc, fsrc);
     }
     COMMIT_MARK("records");
-    segment_records(s, seg, nseg, use_tree, plan, h);
+    if (!forest.on) segment_records(s, seg, nseg, use_tree, plan, h);
     if (int rc = assign_leaf_ids(opt.threads, h, err)) return rc;
     COMMIT_MARK("leaves");
     shade_fields(s, opt.threads, h);

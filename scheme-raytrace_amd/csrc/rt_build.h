@@ -93,6 +93,7 @@ struct HostScene {
     // the device (lds4, ring_waves, ovf_lanes) zero
     DevScene d{};
     bool generic = false;             // the world tree holds generic leaves (gleaf, leaf_pos, rot)
+    bool forest = false;              // a media forest: one generic tree per segment; implies generic
     rt_tree_info tree{};
     double sah_ms = 0.0;              // the SAH builds' wall time, on `threads` host threads
     int threads = 1;

@@ -30,7 +30,8 @@ constexpr int kLeafTypes = 8;
 constexpr int32_t GROUP_BVH = 8;               // group type: BVH over world-level spheres / curves
 // closest-hit kernel variants: scene features compiled in (extra = constant media, Klein limit sets)
 // kFeatGeneric: the world tree holds generic leaves (rects, instanced spheres: DevScene::gleaf); such scenes
-// have no curves, media or Klein sets, so the bit is never combined with the other two
+// have no curves or Klein sets.  kFeatGeneric | kFeatExtra: a media forest, one generic tree per segment of
+// the list between constant media; the only combination the bit enters
 constexpr int kFeatCurves = 1, kFeatExtra = 2, kFeatGeneric = 4;
 enum ChainOp : int32_t { OP_TRANSLATE = 0, OP_ROTATE_Y = 1 };
 
@@ -119,6 +120,9 @@ struct RotEntry { int32_t n, axes; double sc[kMaxChain][2]; };   // (sin, cos) p
 // One group = leaves [begin, end) of one type under one chain (-1 = world).
 struct Group { int32_t type, chain, begin, end; };   // begin/end index the type array
                                                       // leaf id = leaf_base[type] + local
+// A media forest's GROUP_BVH groups carry their tree: begin = its root child ref in bvh2 / bleaf, end = the
+// root of its time-0 twin in g0bvh2 / g0bleaf, or kNoTwin (no moving sphere in the tree)
+constexpr int32_t kNoTwin = INT32_MIN;
 
 // Light sampling target for the pdf.scm mixture (extension f2): an axis rect
 // (axis as LeafType rect order) or a sphere.  type 0 = off.
@@ -200,8 +204,8 @@ struct DevScene {
     int32_t mat_mask;                          // bit t set <=> some material of type t exists
     DevCamera cam;
     DevLight light;
-    // the world's leaf ids in list order (hit-obj-list's order; 0 entries in scenes with media): what a ray
-    // that lies in a rect's plane is scanned in (list_closest)
+    // the world's leaf ids in list order (hit-obj-list's order; 0 entries in scenes with media, except media
+    // forests, whose list holds the media too): what a ray that lies in a rect's plane is scanned in (list_closest)
     const int32_t* order;  int32_t n_order;
     // image textures (t:image-texture, texture.scm:36-50): every image's texels in one buffer, one dword per
     // texel (R | G << 8 | B << 16), so a lookup is one load; has_image_tex selects the kernels' kTexImage instances
@@ -215,6 +219,9 @@ struct DevScene {
     // position in the flattened list, which decides between hits at one t (tie_take).  rot: the
     // rotation sequences of the tree rects' chains with the local axes their planes are normal to; a
     // ray whose local direction is exactly zero on such an axis takes list_closest (order_dependent).
+    // Media forests (n_gleaf > 0 and n_med > 0): bvh2 / bleaf, g0bvh2 / g0bleaf and gleaf hold every
+    // segment's tree one after the other, each entered at the roots its GROUP_BVH group carries (kNoTwin);
+    // leaf_pos and order cover the media; rot covers the rects of all trees.
     const int32_t* gleaf;  int32_t n_gleaf;
     const int32_t* leaf_pos;
     const BvhNode2* g0bvh2; const BvhLeaf* g0bleaf; int32_t g0bvh2_root, n_g0bvh2;

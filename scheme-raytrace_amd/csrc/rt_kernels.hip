@@ -27,8 +27,9 @@
 // F selects the closest-hit features compiled in (kFeatCurves: curve batching
 // state; kFeatExtra: constant media and Klein limit sets, which draw random
 // numbers / march inside the hit test; kFeatGeneric, on its own: a world tree
-// of rects and instanced spheres, bvh_closest_generic), so sphere scenes run
-// lean kernels.
+// of rects and instanced spheres, bvh_closest_generic; kFeatGeneric |
+// kFeatExtra: a media forest, one such tree per segment of the list between
+// constant media), so sphere scenes run lean kernels.
 //
 // All arithmetic is f64 like the reference's flonums.  Random numbers come
 // from a Philox4x32-10 stream keyed by (seed, pixel, sample) with a per-path
@@ -1518,6 +1519,9 @@ __device__ __forceinline__ TreeA treeA_hbm(const DevScene& sc) { return TreeA{sc
 // list order a sphere takes the hit only with t < closest and a rect unless t > closest: of the elements
 // at the smallest t the last rect wins, and the first sphere when none of them is a rect.  tie_take: does
 // leaf `id` (a rect or not) at t == closest take the hit from `best`?  Only reached on exact ties.
+// Media forests: `best` may be a medium.  A medium is scanned after its segment's leaves and before every
+// later segment's, and leaf_pos covers it, so `id` is later in the list: a rect takes the hit (!brect) and
+// a sphere does not (its position is the larger one), as the list decides.
 __device__ __noinline__ bool tie_take(const DevScene& sc, const int32_t best, const int32_t id, const bool rect) {
     if (best < 0) return rect;                             // closest is still t-max: only a rect passes t <= closest
     const int32_t bt = sc.leaves[best].type;
@@ -1725,12 +1729,15 @@ __device__ __forceinline__ void group_closest(const DevScene& sc, const Group& G
 // whatever came before, and lets every later rect in bounds pass `t > closest` — so the grouped scan above,
 // which meets the leaves by (chain, type), can end on another object.  Each leaf's test is the one the
 // groups and the tree walks run (the same operations on the same records).  Scenes with media keep the
-// grouped scan (their hit test draws random numbers; n_order is 0).
+// grouped scan (their hit test draws random numbers; n_order is 0) — except media forests (kFeatGeneric |
+// kFeatExtra), whose list holds the media: each is tested at its position against the running closest and
+// draws from the path's stream there, as hit-obj-list does.
 template <int F>
 __device__ __forceinline__ void list_closest(const DevScene& sc, const v3 o0, const v3 d0, const double time,
-                                             double& closest, int32_t& best) {
+                                             double& closest, int32_t& best, Rng* rng = nullptr) {
     constexpr bool BEZ = (F & kFeatCurves) != 0;
     constexpr bool MED = (F & kFeatExtra) != 0;
+    constexpr bool FOREST = MED && (F & kFeatGeneric) != 0;
     closest = kTmax;
     best = -1;
     for (int k = 0; k < sc.n_order; ++k) {
@@ -1772,6 +1779,9 @@ __device__ __forceinline__ void list_closest(const DevScene& sc, const v3 o0, co
             const double A = oa + t * da, Bv = ob + t * db;
             if (A < R.a0 || A > R.a1 || Bv < R.b0 || Bv > R.b1) continue;
             closest = t; best = id;
+        } else if constexpr (FOREST) {
+            double t;
+            if (medium_test(sc, sc.med[s], o0, d0, d, time, closest, *rng, t)) { closest = t; best = id; }
         }
     }
 }
@@ -1783,20 +1793,28 @@ __device__ __forceinline__ int32_t closest_hit(const DevScene& sc, const v3 o0, 
                                                const TreeA ta) {
     constexpr bool BEZ = (F & kFeatCurves) != 0;
     constexpr bool GEN = (F & kFeatGeneric) != 0;
+    constexpr bool FOREST = GEN && (F & kFeatExtra) != 0;    // a media forest: one generic tree per segment
     int32_t best = -1;
     bool nan_t = false;
     closest = kTmax;
+    uint32_t ctr0 = 0u;                                       // FOREST: the stream's counter before the scan
     if constexpr (GEN) {
-        static_assert(sizeof(SE) == 4 && F == kFeatGeneric, "generic tree leaves: the HBM walk, no curves or media");
+        static_assert(sizeof(SE) == 4 && !BEZ, "generic tree leaves: the HBM walk, no curves");
+        if constexpr (FOREST) ctr0 = rng->ctr;
         if (order_dependent(sc, o0, d0)) {                      // the list's order decides
-            list_closest<F>(sc, o0, d0, time, closest, best);
+            list_closest<F>(sc, o0, d0, time, closest, best, rng);
             return best;
         }
     }
     for (int g = 0; g < sc.n_groups; ++g) {
         const Group G = sc.groups[g];
         if (G.type == GROUP_BVH) {
-            if constexpr (GEN) {
+            if constexpr (FOREST) {                             // the group carries its tree's roots
+                const bool twin = G.end != kNoTwin && __double_as_longlong(time) == 0ll;
+                bvh_closest_generic(sc, o0, d0, time, closest, best, lstk, lmax, twin ? sc.g0bvh2 : sc.bvh2,
+                                    twin ? sc.g0bleaf : sc.bleaf, twin ? G.end : G.begin);
+                continue;
+            } else if constexpr (GEN) {
                 if (sc.g0bvh2 != nullptr && __double_as_longlong(time) == 0ll)
                     bvh_closest_generic(sc, o0, d0, time, closest, best, lstk, lmax, sc.g0bvh2, sc.g0bleaf, sc.g0bvh2_root);
                 else
@@ -1813,6 +1831,13 @@ __device__ __forceinline__ int32_t closest_hit(const DevScene& sc, const v3 o0, 
             continue;
         }
         group_closest<F>(sc, G, o0, d0, time, closest, best, rng, &nan_t);
+    }
+    if constexpr (FOREST) {                  // a rect outside the trees met an in-plane ray: the list from the start,
+        if (nan_t && sc.n_order > 0) {       // the media's draws taken again from where the scan began
+            rng->ctr = ctr0;
+            list_closest<F>(sc, o0, d0, time, closest, best, rng);
+        }
+        return best;
     }
     if (nan_t && sc.n_order > 0) list_closest<F>(sc, o0, d0, time, closest, best);   // the list's order decides
     return best;
@@ -2036,6 +2061,31 @@ __global__ __launch_bounds__(256) void k_hit_rays(const DevScene sc, const doubl
                                         nullptr, tree0_hbm(sc), treeA_hbm(sc));
     out_t[k] = leaf < 0 ? 0.0 : t;
     out_mat[k] = leaf < 0 ? -1 : sc.leaves[leaf].mat;
+}
+
+// k_hit_rays with the path's random stream (rt_hit_rays_stream): ray k carries the stream of (seed, pixel k,
+// sample 0) from counter 0, as a camera ray of that pixel's first sample would before its own draws, and
+// the number of draws the query took is reported.  Scenes with media included: their hit tests draw here
+// as they do in k_extend.
+template <int F>
+__global__ __launch_bounds__(256) void k_hit_rays_stream(const DevScene sc, const double* __restrict__ rays, uint32_t n,
+                                                         const uint32_t k0, const uint32_t k1, double* __restrict__ out_t,
+                                                         int32_t* __restrict__ out_mat, int32_t* __restrict__ out_draws) {
+    extern __shared__ uint32_t s_lstack[];
+    constexpr bool BEZ = (F & kFeatCurves) != 0;
+    __shared__ BezWave s_bw[BEZ ? 4 : 1];
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= n) return;
+    const double* r = rays + 7 * (size_t)k;
+    double t = 0.0;
+    Rng g;
+    g.init(k0, k1, k, 0u, 0u);
+    const int32_t leaf = closest_hit<F>(sc, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), r[6], t,
+                                        s_lstack + threadIdx.x, sc.lane_stack, &s_bw[BEZ ? (threadIdx.x >> 6) : 0],
+                                        &g, tree0_hbm(sc), treeA_hbm(sc));
+    out_t[k] = leaf < 0 ? 0.0 : t;
+    out_mat[k] = leaf < 0 ? -1 : sc.leaves[leaf].mat;
+    out_draws[k] = (int32_t)g.ctr;
 }
 
 // Wave-level append into the sharded material queues (block_append's layout:
@@ -3409,7 +3459,8 @@ static bool finish_generic() {               // RTAMD_FINISH_GENERIC: the group-
     return e != nullptr && e[0] != '0';
 }
 static int scene_features(const DevScene& sc) {
-    if (sc.n_gleaf > 0) return kFeatGeneric;         // (commit_scene: never with curves, media or Klein sets)
+    // (build_scene: generic leaves never with curves or Klein sets; with media only in a media forest)
+    if (sc.n_gleaf > 0) return sc.n_med > 0 ? kFeatGeneric | kFeatExtra : kFeatGeneric;
     return (sc.n_bez > 0 ? kFeatCurves : 0) | (sc.n_med > 0 || sc.n_klein > 0 ? kFeatExtra : 0);
 }
 static int scene_tex_level(const DevScene& sc) {     // the instances a scene's launches take
@@ -3453,6 +3504,7 @@ using ExtendLdsKernel = void (*)(DevScene, RenderParams, PathState, QView, uint3
 using CameraKernel = void (*)(DevScene, RenderParams, PathState, uint32_t, HitBuf, uint32_t, uint32_t*, uint32_t,
                               unsigned long long*);
 using HitRaysKernel = void (*)(DevScene, const double*, uint32_t, double*, int32_t*);
+using HitRaysStreamKernel = void (*)(DevScene, const double*, uint32_t, uint32_t, uint32_t, double*, int32_t*, int32_t*);
 using HitRaysLdsKernel = void (*)(DevScene, const double*, uint32_t, double*, int32_t*, uint32_t);
 using ShadeKernel = void (*)(const DevScene*, RenderParams, PathState, const HitRec*, QView, PathState, uint32_t*,
                              uint32_t, uint32_t);
@@ -3461,6 +3513,7 @@ using FinishKernel = void (*)(const DevScene*, RenderParams, PathState, QView, u
 using FeaturesKernel = void (*)(DevScene, RenderParams, uint32_t, double*);
 static ExtendKernel extend_kernel(const DevScene& sc) {
     if (scene_features(sc) == kFeatGeneric) return k_extend<kFeatGeneric>;
+    if (scene_features(sc) == (kFeatGeneric | kFeatExtra)) return k_extend<kFeatGeneric | kFeatExtra>;
     return dispatch([](auto F) -> ExtendKernel { return k_extend<F()>; }, UpTo<3>{scene_features(sc)});
 }
 // FUSE: 0 one depth, 1 every depth from fuse->depth on with the device libm, 2 with the exact libm
@@ -3479,6 +3532,12 @@ static CameraKernel camera_kernel(const DevScene& sc) {
 static HitRaysKernel hit_rays_kernel(const DevScene& sc) {
     if (scene_features(sc) == kFeatGeneric) return k_hit_rays<kFeatGeneric>;
     return scene_features(sc) ? k_hit_rays<kFeatCurves | kFeatExtra> : k_hit_rays<0>;
+}
+static HitRaysStreamKernel hit_rays_stream_kernel(const DevScene& sc) {
+    const int f = scene_features(sc);
+    if (f == (kFeatGeneric | kFeatExtra)) return k_hit_rays_stream<kFeatGeneric | kFeatExtra>;
+    if (f == kFeatGeneric) return k_hit_rays_stream<kFeatGeneric>;
+    return f ? k_hit_rays_stream<kFeatCurves | kFeatExtra> : k_hit_rays_stream<0>;
 }
 // the probe of k_extend_lds's walk (time0) or k_camera's: the instance with that kernel's arguments
 static HitRaysLdsKernel hit_rays_lds_kernel(const DevScene& sc, const bool time0) {
@@ -3518,6 +3577,10 @@ static FinishKernel finish_kernel(const DevScene& sc, const RenderParams& rp, co
         return dispatch([](auto IMG, auto EX) -> FinishKernel {
             return k_finish<kFeatGeneric, IMG() ? kTexImage : kTexPerlin, true, false, EX()>;
         }, tl == kTexImage, ex);
+    if (f == (kFeatGeneric | kFeatExtra))
+        return dispatch([](auto IMG, auto EX) -> FinishKernel {
+            return k_finish<kFeatGeneric | kFeatExtra, IMG() ? kTexImage : kTexPerlin, true, false, EX()>;
+        }, tl == kTexImage, ex);
     if (f > 0)
         return dispatch([](auto F1, auto IMG, auto EX) -> FinishKernel {
             return k_finish<F1() + 1, IMG() ? kTexImage : kTexPerlin, true, false, EX()>;
@@ -3528,6 +3591,9 @@ static FinishKernel finish_kernel(const DevScene& sc, const RenderParams& rp, co
 static FeaturesKernel features_kernel(const DevScene& sc) {
     if (scene_features(sc) == kFeatGeneric)
         return dispatch([](auto TL) -> FeaturesKernel { return k_features<kFeatGeneric, TL()>; }, TexLevel{scene_tex_level(sc)});
+    if (scene_features(sc) == (kFeatGeneric | kFeatExtra))
+        return dispatch([](auto TL) -> FeaturesKernel { return k_features<kFeatGeneric | kFeatExtra, TL()>; },
+                        TexLevel{scene_tex_level(sc)});
     return dispatch([](auto F, auto TL) -> FeaturesKernel { return k_features<F(), TL()>; },
                   UpTo<3>{scene_features(sc)}, TexLevel{scene_tex_level(sc)});
 }
@@ -3583,6 +3649,14 @@ hipError_t launch_hit_rays(const DevScene& sc, const double* rays, uint32_t n, d
     const uint32_t blocks = (n + 255u) / 256u;
     if (!blocks) return hipSuccess;
     hipLaunchKernelGGL(hit_rays_kernel(sc), dim3(blocks), dim3(256), lane_stack_lds(sc), s, sc, rays, n, out_t, out_mat);
+    return hipGetLastError();
+}
+hipError_t launch_hit_rays_stream(const DevScene& sc, const double* rays, uint32_t n, uint32_t k0, uint32_t k1,
+                                  double* out_t, int32_t* out_mat, int32_t* out_draws, hipStream_t s) {
+    const uint32_t blocks = (n + 255u) / 256u;
+    if (!blocks) return hipSuccess;
+    hipLaunchKernelGGL(hit_rays_stream_kernel(sc), dim3(blocks), dim3(256), lane_stack_lds(sc), s, sc, rays, n, k0, k1,
+                       out_t, out_mat, out_draws);
     return hipGetLastError();
 }
 hipError_t launch_features(const DevScene& sc, const RenderParams& rp, uint32_t S, double* feat, hipStream_t s) {

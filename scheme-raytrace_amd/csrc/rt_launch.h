@@ -52,6 +52,10 @@ hipError_t launch_curve_depth(const double* cps, const double* eps8, uint32_t n,
 // rt_hit_rays: n rays of 7 doubles (origin, direction, time); the closest hit's t and material
 hipError_t launch_hit_rays(const DevScene& sc, const double* rays, uint32_t n, double* out_t, int32_t* out_mat,
                            hipStream_t s);
+// rt_hit_rays_stream: the same query with ray k on the path stream (k0, k1; pixel k, sample 0) from counter 0;
+// out_draws: the random numbers each query took
+hipError_t launch_hit_rays_stream(const DevScene& sc, const double* rays, uint32_t n, uint32_t k0, uint32_t k1,
+                                  double* out_t, int32_t* out_mat, int32_t* out_draws, hipStream_t s);
 // rt_hit_rays_walk's LDS walks: the same rays through k_extend_lds's query (time0: every ray at time +0.0)
 // or k_camera's, in the instance those kernels' launchers pick for the scene; lds: the scene's
 // extend_lds_bytes (time0) / camera_lds_bytes, not 0

@@ -587,6 +587,35 @@ int rt_hit_rays_walk(int scene, int walk, int n, const double* rays, double* out
     return 0;
 }
 
+int rt_hit_rays_stream(int scene, const double* rays, int n, uint64_t seed, double* out_t, int32_t* out_mat,
+                       int32_t* out_draws) {
+    LOCK_SCENE(s, scene);
+    if (!s->committed) return fail("scene not committed (rt_scene_commit)");
+    if (n < 0) return fail("ray count must be >= 0");
+    if (n > 0 && (!rays || !out_t || !out_mat || !out_draws)) return fail("null pointer");
+    CTX_OF(c, s);
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    uint32_t stale = 0;
+    HIPCHK(take_fault(&stale));
+    DevBuf d_rays, d_t, d_mat, d_draws;
+    HIPCHK(d_rays.ensure((size_t)n * 7 * sizeof(double)));
+    HIPCHK(d_t.ensure((size_t)n * sizeof(double)));
+    HIPCHK(d_mat.ensure((size_t)n * sizeof(int32_t)));
+    HIPCHK(d_draws.ensure((size_t)n * sizeof(int32_t)));
+    HIPCHK(hipMemcpyAsync(d_rays.p, rays, (size_t)n * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_hit_rays_stream(s->dev, d_rays.as<const double>(), (uint32_t)n, (uint32_t)seed, (uint32_t)(seed >> 32),
+                                  d_t.as<double>(), d_mat.as<int32_t>(), d_draws.as<int32_t>(), c->stream));
+    HIPCHK(hipMemcpyAsync(out_t, d_t.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out_mat, d_mat.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out_draws, d_draws.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    uint32_t f = 0;
+    HIPCHK(take_fault(&f));
+    if (f) return fail(fault_text(f));
+    return 0;
+}
+
 int rt_curve_depth_probe(int ctx, int n, const double* cps, const double* eps8, int32_t* out_depth) {
     LOCK_CTX(c, ctx);
     if (n < 0) return fail("curve count must be >= 0");

@@ -62,10 +62,10 @@ class RtSceneInfo(ctypes.Structure):
 
 
 class RtTreeInfo(ctypes.Structure):
-    """rt_tree_info (RT_HAS_GENERIC_BVH): which leaves the world tree took."""
+    """rt_tree_info (RT_HAS_GENERIC_BVH): which leaves the world tree took (media forests: the trees)."""
     _fields_ = [(n, ctypes.c_int32) for n in ("sphere_leaves", "curve_leaves", "generic_leaves", "group_leaves",
                                               "nodes", "depth", "nodes0", "depth0", "rot_entries",
-                                              "generic_min")] + [("reserved", ctypes.c_int32 * 6)]
+                                              "generic_min", "segments", "segment_trees")] + [("reserved", ctypes.c_int32 * 4)]
 
 
 class RtAdaptive(ctypes.Structure):
@@ -102,6 +102,9 @@ _SIGNATURES = {
                     ctypes.POINTER(ctypes.c_int32)],
     "rt_hit_rays_walk": [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                          ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)],
+    "rt_hit_rays_stream": [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_uint64,    # RT_HAS_MEDIA_BVH
+                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32),
+                           ctypes.POINTER(ctypes.c_int32)],
     "rt_scene_begin": [ctypes.c_int, _c_int_p],
     "rt_scene_destroy": [ctypes.c_int],
     "rt_add_texture_constant": [ctypes.c_int, _c_double_p, _c_int_p],

@@ -212,8 +212,9 @@ def scene_info(scene_handle):
 
 def tree_info(scene_handle):
     """rt_get_tree_info as a dict: the leaves the world tree took (world-level spheres, curves, generic
-    leaves), those left in brute-force groups, the trees' sizes, the rotation table's entries and the
-    RTAMD_BVH_GENERIC_MIN in force at the commit."""
+    leaves), those left in brute-force groups, the trees' sizes, the rotation table's entries, the
+    RTAMD_BVH_GENERIC_MIN in force at the commit, and for a media forest its segments and how many got a tree
+    (both 0 otherwise)."""
     s = _lib.RtTreeInfo()
     call("rt_get_tree_info", scene_handle, ctypes.byref(s))
     return {name: getattr(s, name) for name, _ in s._fields_ if name != "reserved"}
@@ -297,6 +298,22 @@ def hit_rays(scene, rays, ctx=None, walk=WALK_HBM):
     call("rt_hit_rays_walk", h, int(walk), n, r.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
          t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), m.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
     return t, m
+
+
+def hit_rays_stream(scene, rays, seed, ctx=None):
+    """rt_hit_rays_stream: hit_rays in device memory with ray k on the path stream (seed, pixel k, sample 0);
+    returns (t, material id, draws) arrays, draws = the random numbers each query consumed.  Takes scenes
+    with constant media too."""
+    h = upload(scene, ctx)
+    r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 7)
+    n = r.shape[0]
+    t = np.zeros(n)
+    m = np.zeros(n, dtype=np.int32)
+    draws = np.zeros(n, dtype=np.int32)
+    call("rt_hit_rays_stream", h, r.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n,
+         ctypes.c_uint64(seed & (2**64 - 1)), t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+         m.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), draws.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    return t, m, draws
 
 
 def resolve_u8(accum, nx, ny, sample_count):

@@ -348,7 +348,8 @@ def cornell_curves_small(nx, ny):
 NEXT_WEEK_SEED = 0x5EED0007
 
 
-def next_week(nx, ny, seed=NEXT_WEEK_SEED, perlin_seed=PERLIN_SEED, boxes_per_side=20, cluster=1000, earth=True):
+def next_week(nx, ny, seed=NEXT_WEEK_SEED, perlin_seed=PERLIN_SEED, boxes_per_side=20, cluster=1000, earth=True,
+              media=False, media_density=(0.2, 0.0001)):
     """The closing scene of "Ray Tracing: The Next Week", written with the reference's constructors: a field
     of boxes_per_side^2 ground boxes of seeded random heights under make-bvh-node, the ceiling light, a moving
     sphere, a glass and a metal sphere, a second glass sphere (the book's medium boundary), an image-textured
@@ -356,10 +357,13 @@ def next_week(nx, ny, seed=NEXT_WEEK_SEED, perlin_seed=PERLIN_SEED, boxes_per_si
     (the book puts the two transforms around the node; the reference's rotate-y and translate take the hit's
     material from the object they wrap, geometry.scm:537, which a bvh node does not have — wrapped sphere by
     sphere the reference can express the scene, and the library flattens both forms to the same leaves under
-    one instance chain).  The book's
-    two constant media (the blue volume inside the second glass sphere and the thin mist around everything)
-    are left out: a medium's hit test draws random numbers in list order, and scenes with one keep the
-    brute-force groups (include/rt.h, rt_add_bvh).  Black sky, shutter [0, 1].  earth=False: the globe takes a
+    one instance chain).  media=True adds the book's two constant media where the book lists them: after the
+    second glass sphere the blue volume inside it (density 0.2, albedo (0.2, 0.4, 0.9), bounded by an equal
+    sphere), then the thin mist around everything (density 0.0001, white, a sphere of radius 5000 at the
+    origin); media_density: the two densities.  A medium's hit test draws random numbers in list order, so
+    the list is cut into segments at the media and each segment gets a tree of its own (a media forest:
+    include/rt.h, rt_add_bvh; DESIGN.md 4.9).  The default leaves them out (SCENES["next_week"]);
+    SCENES["next_week_media"] is the full scene.  Black sky, shutter [0, 1].  earth=False: the globe takes a
     checker texture instead of its image (the oracle restates no image textures)."""
     import numpy as np
 
@@ -392,6 +396,15 @@ def next_week(nx, ny, seed=NEXT_WEEK_SEED, perlin_seed=PERLIN_SEED, boxes_per_si
         g.make_sphere(v.vec3(260, 150, 45), 50, g.make_dielectric(1.5)),
         g.make_sphere(v.vec3(0, 150, 145), 50, g.make_metal(g.constant_texture(v.vec3(0.8, 0.8, 0.9)), 1.0)),
         g.make_sphere(v.vec3(360, 150, 145), 70, g.make_dielectric(1.5)),
+    ]
+    if media:
+        objs += [
+            g.make_constant_medium(g.make_sphere(v.vec3(360, 150, 145), 70, g.make_dielectric(1.5)), media_density[0],
+                                   g.constant_texture(v.vec3(0.2, 0.4, 0.9))),
+            g.make_constant_medium(g.make_sphere(v.vec3(0, 0, 0), 5000, g.make_dielectric(1.5)), media_density[1],
+                                   g.constant_texture(v.vec3(1, 1, 1))),
+        ]
+    objs += [
         g.make_sphere(v.vec3(400, 200, 400), 100, g.make_lambertian(globe)),
         g.make_sphere(v.vec3(220, 280, 300), 80, g.make_lambertian(g.marble_texture(0.1))),
         g.make_bvh_node(small, 0, 1),
@@ -400,8 +413,14 @@ def next_week(nx, ny, seed=NEXT_WEEK_SEED, perlin_seed=PERLIN_SEED, boxes_per_si
     return g.make_scene(objs, cam, g.black, perlin=_perlin.from_seed(perlin_seed))
 
 
+def next_week_media(nx, ny, **kw):
+    """next_week with the book's two constant media (media=True)."""
+    return next_week(nx, ny, media=True, **kw)
+
+
 SCENES = {
     "next_week": next_week,
+    "next_week_media": next_week_media,
     "cover": random_scene,
     "cover_marble": marble_random_scene,
     "test_scene": test_scene,

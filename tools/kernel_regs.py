@@ -3,7 +3,7 @@
 assembly (make -C scheme-raytrace_amd/csrc asm -> rt_kernels.s, rt_frame.s).
 usage: python tools/kernel_regs.py [file.s ...] [name-filter]   (default: both files)
 The last column is a hash of the kernel's instruction text with the function-numbered local labels
-(.LBB<n>_, .Lfunc_end<n>, ...) normalised, so two builds' kernels compare whatever else the files hold."""
+(.LBB<n>_, .Lfunc_end<n>, .Lpost_getpc<n>, ...) normalised, so two builds' kernels compare whatever else the files hold."""
 import hashlib
 import re
 import sys
@@ -13,7 +13,7 @@ def text_hashes(s):
     """kernel name -> hash of its body (label line to .Lfunc_end), local label numbers dropped"""
     out = {}
     for m in re.finditer(r"^(\w+):.*?\n(.*?)^\.Lfunc_end\d+:", s, re.M | re.S):
-        body = re.sub(r"\.L(BB|func_begin|func_end|JTI|tmp)\d+", r".L\1", m.group(2))
+        body = re.sub(r"\.L(BB|func_begin|func_end|JTI|tmp|post_getpc)\d+", r".L\1", m.group(2))
         body = "\n".join(ln.split(";")[0].rstrip() for ln in body.splitlines())      # comments name the labels too
         out[m.group(1)] = hashlib.sha1(body.encode()).hexdigest()[:12]
     return out
@@ -45,6 +45,7 @@ if __name__ == "__main__":
         found.update(kernels(path))
     for name, f in sorted(found.items()):
         if flt in name:
-            print("%-90s vgpr %3d agpr %3d spill %3d lds %6d scratch %4d text %s" % (
-                name[:90], f.get("vgpr_count", 0), f.get("agpr_count", 0), f.get("vgpr_spill_count", 0),
+            print("%-90s vgpr %3d agpr %3d sgpr %3d spill %3d+%d lds %6d scratch %4d text %s" % (
+                name[:90], f.get("vgpr_count", 0), f.get("agpr_count", 0), f.get("sgpr_count", 0),
+                f.get("vgpr_spill_count", 0), f.get("sgpr_spill_count", 0),
                 f.get("group_segment_fixed_size", 0), f.get("private_segment_fixed_size", 0), f["text"]))
