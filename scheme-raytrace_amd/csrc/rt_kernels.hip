@@ -279,6 +279,11 @@ __device__ __forceinline__ void sphere_test(const v3 o, const v3 d, const double
         if (kTmin < t && t < closest) { closest = t; best = id; }
     }
 }
+// center(time) of a moving sphere (geometry.scm:181-184): c0 + dc * frac, frac = (time - t0) / den.  How the
+// quotient is obtained (hoisted, DevScene::msph_shared, or LeafInfo's centre at time 0) is the caller's.
+__device__ __forceinline__ v3 msphere_center(const MSphereRec& S, const double frac) {
+    return mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * frac;
+}
 
 
 // ------------------------------------------------------------- curves
@@ -1129,60 +1134,44 @@ __device__ __forceinline__ void node_hit_signed(const SlabPtr& sp, const uint32_
     hr = tr <= fr;
 }
 
-// FROZEN: the time-0 tree (DevScene::fbvh2), whose leaves hold plain sphere
-// records (moving spheres at center(0)); otherwise the all-times tree.
-// nodes / leaves / fsph may point into LDS (k_extend_lds) or HBM.
 __device__ __forceinline__ int32_t stack_ref(const uint32_t e) { return (int32_t)e; }
 __device__ __forceinline__ int32_t stack_ref(const uint16_t e) { return (int32_t)(int16_t)e; }   // sign: leaf refs < 0
-// SE: stack entry type — uint32_t, or uint16_t (k_extend_lds / k_camera, trees
-// under 32768 nodes and leaves: child refs fit int16, halving the LDS stack).
-// DIRECT (FROZEN only, DevScene::bvh_solo): every time-0 leaf holds one
-// sphere and fsph is in leaf order, so leaf ref ~k tests fsph[k] directly
-// (no leaf record to fetch or keep in LDS).
-// WIDE: the box ray from anywhere (BoxRayW; scenes with curves, whose rays may start far outside)
-template <bool FROZEN, class SE = uint32_t, bool DIRECT = false, bool WIDE = false>
-__device__ __forceinline__ void bvh_closest_lane(const DevScene& sc, const v3 o, const v3 d, const double time,
-                                                 double& closest, int32_t& best, SE* lstk, const int lmax,
-                                                 const BvhNode2* __restrict__ nodes,
-                                                 const BvhLeaf* __restrict__ leaves,
-                                                 const SphereRec* __restrict__ fsph,
-                                                 const SphereRec* __restrict__ sph = nullptr,
-                                                 const MSphereRec* __restrict__ msph = nullptr,
-                                                 const int32_t* __restrict__ fid = nullptr) {
+// The per-lane BVH2 walk every sphere tree and generic tree takes, stated once: descend to a leaf and
+// park it, until every active lane of the wave has one parked (the ballot) or has run out of nodes; then
+// the leaf step runs on the parked leaves together, and the box range shrinks to the new closest (tcap).
+// The far child of a node whose two boxes are hit goes on the lane's stack (lstk: entries blockDim.x
+// apart, lmax deep; a full stack drops the far child, as lane_stack is sized not to).
+// leaf(k): the caller's step for leaf ref ~k.  Every loop is bounded by the tree: a lane enters a node at
+// most once.  SE: stack entry type — uint32_t, or uint16_t (k_extend_lds / k_camera, trees under 32768
+// nodes and leaves: child refs fit int16, halving the LDS stack).  SIGNED: sign-selected planes (the
+// time-0 tree's 16-bit walks).  br: the box ray, BoxRay or from anywhere (BoxRayW; scenes with curves, whose
+// rays may start far outside).  wc: nodes, inner and outer iterations for the stats build.
+struct WalkCount { StatCount node{}, inner{}, outer{}; };
+template <bool SIGNED, class BR, class SE, class Leaf>
+__device__ __forceinline__ void bvh_walk(const BR br, const double& closest, SE* lstk, const int lmax,
+                                         const BvhNode2* __restrict__ nodes, const int32_t root, WalkCount& wc,
+                                         Leaf&& leaf) {
     constexpr int32_t kDone = INT32_MIN;
-    const double a = dot(d, d), ia = 1.0 / a;
-    // 16-bit stacks: the LDS-tree walks; sign-selected planes for the time-0 tree only
-    constexpr bool SIGNED = sizeof(SE) == 2 && FROZEN;
-    static_assert(!(WIDE && SIGNED), "the sign-selected LDS walks serve scenes without curves only");
-    using BR = typename std::conditional<WIDE, BoxRayW, BoxRay>::type;
-    BR br;
-    if constexpr (WIDE) br = box_ray_w(o, d);
-    else br = box_ray(o, d);
+    static_assert(!(std::is_same<BR, BoxRayW>::value && SIGNED), "the sign-selected LDS walks serve scenes without curves only");
     SlabPtr slp{};
     if constexpr (SIGNED) slp = slab_ptr(nodes, slab_off(br));
-    const int32_t bs = sc.leaf_base[LEAF_SPHERE], bm = sc.leaf_base[LEAF_MSPHERE];
     const uint32_t stride = blockDim.x;
-    int32_t fbest = -1;                                       // FROZEN: fsph index of the best hit
-    // moving spheres sharing one shutter: center(time)'s (time - t0) / den is
-    // the same quotient for all of them, computed once (geometry.scm:181-184)
-    const double frac_shared = (!FROZEN && sc.msph_shared) ? (time - sc.msph_t0) / sc.msph_den : 0.0;
     // stack pointer as an element offset (entries sit stride apart): push / pop
     // add or subtract stride instead of multiplying the depth by it
     uint32_t sp = 0;
     const uint32_t slim = (uint32_t)lmax * stride;
-    int32_t node = FROZEN ? sc.fbvh2_root : sc.bvh2_root, pend = kDone;
+    int32_t node = root, pend = kDone;
     float tcap = f32_up(closest);                              // box t range, updated after each leaf
-    StatCount n_node{}, n_leaf{}, n_sph{}, n_msph{}, n_inner{}, n_outer{};
     while (node != kDone || pend != kDone) {
-        ++n_outer;
+        ++wc.outer;
         while (node != kDone) {
-            ++n_inner;
+            ++wc.inner;
             if (node < 0) {                                   // a leaf
                 if (pend != kDone) break;                     // one is already parked
                 pend = node;
                 node = sp ? stack_ref(lstk[sp -= stride]) : kDone;
             } else {
-                ++n_node;
+                ++wc.node;
                 float tl, tr;
                 bool hl, hr;
                 int2 N;                                       // child refs (l, r)
@@ -1210,41 +1199,75 @@ __device__ __forceinline__ void bvh_closest_lane(const DevScene& sc, const v3 o,
             if (__ballot(pend == kDone) == 0ull) break;
         }
         if (pend != kDone) {
-            if constexpr (DIRECT) {
-                ++n_leaf; ++n_sph;
-                const SphereRec S = fsph[~pend];
-                sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, ~pend, closest, fbest);
-            } else {
-                const BvhLeaf L = leaves[~pend];
-                ++n_leaf;
-                if (FROZEN) {
-                    for (int s = L.sb; s < L.sb + L.sn; ++s) {
-                        ++n_sph;
-                        const SphereRec S = fsph[s];
-                        sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, s, closest, fbest);
-                    }
-                } else {
-                    for (int s = L.sb; s < L.sb + L.sn; ++s) {
-                        ++n_sph;
-                        const SphereRec S = sph[s];
-                        sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, bs + s, closest, best);
-                    }
-                    for (int s = L.mb; s < L.mb + L.mn; ++s) {
-                        ++n_msph;
-                        const MSphereRec S = msph[s];
-                        const double frac = sc.msph_shared ? frac_shared : (time - S.t0) / S.den;
-                        const v3 cen = mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * frac;
-                        sphere_test(o, d, a, ia, cen, S.rr, bm + s, closest, best);
-                    }
-                }
-            }
+            leaf(~pend);
             pend = kDone;
             tcap = f32_up(closest);
         }
     }
+}
+
+// The sphere trees' walk.  FROZEN: the time-0 tree (DevScene::fbvh2), whose leaves hold plain sphere
+// records (moving spheres at center(0)); otherwise the all-times tree.
+// nodes / leaves / fsph may point into LDS (k_extend_lds) or HBM.
+// DIRECT (FROZEN only, DevScene::bvh_solo): every time-0 leaf holds one
+// sphere and fsph is in leaf order, so leaf ref ~k tests fsph[k] directly
+// (no leaf record to fetch or keep in LDS).
+// SE, WIDE: bvh_walk's; 16-bit stacks take the sign-selected planes for the time-0 tree only.
+template <bool FROZEN, class SE = uint32_t, bool DIRECT = false, bool WIDE = false>
+__device__ __forceinline__ void bvh_closest_lane(const DevScene& sc, const v3 o, const v3 d, const double time,
+                                                 double& closest, int32_t& best, SE* lstk, const int lmax,
+                                                 const BvhNode2* __restrict__ nodes,
+                                                 const BvhLeaf* __restrict__ leaves,
+                                                 const SphereRec* __restrict__ fsph,
+                                                 const SphereRec* __restrict__ sph = nullptr,
+                                                 const MSphereRec* __restrict__ msph = nullptr,
+                                                 const int32_t* __restrict__ fid = nullptr) {
+    const double a = dot(d, d), ia = 1.0 / a;
+    constexpr bool SIGNED = sizeof(SE) == 2 && FROZEN;
+    using BR = typename std::conditional<WIDE, BoxRayW, BoxRay>::type;
+    BR br;
+    if constexpr (WIDE) br = box_ray_w(o, d);
+    else br = box_ray(o, d);
+    const int32_t bs = sc.leaf_base[LEAF_SPHERE], bm = sc.leaf_base[LEAF_MSPHERE];
+    int32_t fbest = -1;                                       // FROZEN: fsph index of the best hit
+    // moving spheres sharing one shutter: center(time)'s (time - t0) / den is
+    // the same quotient for all of them, computed once (geometry.scm:181-184)
+    const double frac_shared = (!FROZEN && sc.msph_shared) ? (time - sc.msph_t0) / sc.msph_den : 0.0;
+    WalkCount wc;
+    StatCount n_leaf{}, n_sph{}, n_msph{};
+    bvh_walk<SIGNED>(br, closest, lstk, lmax, nodes, FROZEN ? sc.fbvh2_root : sc.bvh2_root, wc, [&](const int32_t k) {
+        ++n_leaf;
+        if constexpr (DIRECT) {
+            ++n_sph;
+            const SphereRec S = fsph[k];
+            sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, k, closest, fbest);
+        } else {
+            const BvhLeaf L = leaves[k];
+            if (FROZEN) {
+                for (int s = L.sb; s < L.sb + L.sn; ++s) {
+                    ++n_sph;
+                    const SphereRec S = fsph[s];
+                    sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, s, closest, fbest);
+                }
+            } else {
+                for (int s = L.sb; s < L.sb + L.sn; ++s) {
+                    ++n_sph;
+                    const SphereRec S = sph[s];
+                    sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, bs + s, closest, best);
+                }
+                for (int s = L.mb; s < L.mb + L.mn; ++s) {
+                    ++n_msph;
+                    const MSphereRec S = msph[s];
+                    const double frac = sc.msph_shared ? frac_shared : (time - S.t0) / S.den;
+                    sphere_test(o, d, a, ia, msphere_center(S, frac), S.rr, bm + s, closest, best);
+                }
+            }
+        }
+    });
     if (FROZEN && fbest >= 0) best = fid[fbest];
     if constexpr (kStats) {
         constexpr int so = FROZEN ? kStatTree0 : 0;
+        const StatCount n_node = wc.node, n_inner = wc.inner, n_outer = wc.outer;
         stat_add(so + kStatRays, 1); stat_add(so + kStatNodes, n_node); stat_add(so + kStatLeaves, n_leaf);
         stat_add(so + kStatSpheres, n_sph); stat_add(so + kStatMSpheres, n_msph);
         stat_add(so + kStatInner, n_inner); stat_add(so + kStatOuter, n_outer);
@@ -1329,7 +1352,7 @@ __device__ __forceinline__ void bvh_closest_curves(const DevScene& sc, const v3 
                 for (int s = L.mb; s < L.mb + L.mn; ++s) {
                     const MSphereRec S = sc.msph[s];
                     const double frac = (time - S.t0) / S.den;
-                    const v3 cen = mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * frac;
+                    const v3 cen = msphere_center(S, frac);
                     sphere_test(o, d, a, ia, cen, S.rr, bm + s, closest, best);
                 }
                 pb = L.bb; pe = L.bb + L.bn;
@@ -1452,7 +1475,7 @@ __device__ __forceinline__ bool boundary_hit(const DevScene& sc, const MediumRec
                     c = mk(S.cx, S.cy, S.cz); rr = S.rr;
                 } else {
                     const MSphereRec S = sc.msph[s];
-                    c = mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * ((time - S.t0) / S.den);
+                    c = msphere_center(S, (time - S.t0) / S.den);
                     rr = S.rr;
                 }
                 const v3 oc = o - c;
@@ -1568,7 +1591,8 @@ __device__ __forceinline__ bool order_dependent(const DevScene& sc, const v3 o, 
     return dep;
 }
 // One leaf of the world's list against the shrinking closest: list_closest's per-leaf test (the same
-// operations on the same records, so the same t bit for bit), ties by list position.
+// operations on the same records, so the same t bit for bit), ties by list position.  (Two copies on purpose: with
+// one leaf_test<F, TIE> under both, k_extend_curves, through its list_closest<kFeatCurves> fall-back, ran 398 -> 383 Mrays/s.)
 __device__ __forceinline__ void leaf_test_generic(const DevScene& sc, const int32_t id, const v3 o0, const v3 d0,
                                                   const double time, double& closest, int32_t& best) {
     const int4 L = *reinterpret_cast<const int4*>(&sc.leaves[id]);          // type, chain, local, flip
@@ -1583,7 +1607,7 @@ __device__ __forceinline__ void leaf_test_generic(const DevScene& sc, const int3
         const double a = dot(d, d), ia = 1.0 / a;
         const MSphereRec S = sc.msph[s];
         const double frac = (time - S.t0) / S.den;
-        const v3 cen = mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * frac;
+        const v3 cen = msphere_center(S, frac);
         sphere_test_tie(sc, o, d, a, ia, cen, S.rr, id, closest, best);
     } else {
         double ok, dk, oa, da, ob, db;
@@ -1599,53 +1623,19 @@ __device__ __forceinline__ void leaf_test_generic(const DevScene& sc, const int3
         closest = t; best = id;
     }
 }
-// bvh_closest_lane's walk over a tree of generic leaves (nodes / leaves / root: the all-times tree or the
-// time-0 one): the same per-lane traversal, each leaf's gleaf range tested leaf by leaf.  Every loop is
-// bounded by the tree: a lane enters a node at most once, and a leaf's range lies inside gleaf.
+// bvh_walk over a tree of generic leaves (nodes / leaves / root: the all-times tree or the time-0 one): each
+// leaf's gleaf range, clamped to gleaf, tested leaf by leaf.  gleaf holds spheres, moving spheres and rects
+// only, a media forest's too, so the leaf test is kFeatGeneric's whatever the scene's set.
 __device__ __forceinline__ void bvh_closest_generic(const DevScene& sc, const v3 o, const v3 d, const double time,
                                                     double& closest, int32_t& best, uint32_t* lstk, const int lmax,
                                                     const BvhNode2* __restrict__ nodes,
                                                     const BvhLeaf* __restrict__ leaves, const int32_t root) {
-    constexpr int32_t kDone = INT32_MIN;
-    const BoxRay br = box_ray(o, d);
-    const uint32_t stride = blockDim.x;
-    uint32_t sp = 0;
-    const uint32_t slim = (uint32_t)lmax * stride;
-    int32_t node = root, pend = kDone;
-    float tcap = f32_up(closest);
-    while (node != kDone || pend != kDone) {
-        while (node != kDone) {
-            if (node < 0) {                                   // a leaf
-                if (pend != kDone) break;                     // one is already parked
-                pend = node;
-                node = sp ? (int32_t)lstk[sp -= stride] : kDone;
-            } else {
-                float tl, tr;
-                bool hl, hr;
-                const BvhNode2 M = nodes[node];
-                node_hit(M, br, tcap, hl, hr, tl, tr);
-                if (hl && hr) {
-                    const bool lfirst = tl <= tr;
-                    if (sp < slim) { lstk[sp] = (uint32_t)(lfirst ? M.r : M.l); sp += stride; }
-                    node = lfirst ? M.l : M.r;
-                } else if (hl) {
-                    node = M.l;
-                } else if (hr) {
-                    node = M.r;
-                } else {
-                    node = sp ? (int32_t)lstk[sp -= stride] : kDone;
-                }
-            }
-            if (__ballot(pend == kDone) == 0ull) break;       // every active lane has a leaf parked
-        }
-        if (pend != kDone) {
-            const BvhLeaf L = leaves[~pend];
-            const int gb = max(L.gb, 0), ge = min(L.gb + L.gn, sc.n_gleaf);
-            for (int g = gb; g < ge; ++g) leaf_test_generic(sc, sc.gleaf[g], o, d, time, closest, best);
-            pend = kDone;
-            tcap = f32_up(closest);
-        }
-    }
+    WalkCount wc;                                             // (the stats build counts the sphere trees only)
+    bvh_walk<false>(box_ray(o, d), closest, lstk, lmax, nodes, root, wc, [&](const int32_t k) {
+        const BvhLeaf L = leaves[k];
+        const int gb = max(L.gb, 0), ge = min(L.gb + L.gn, sc.n_gleaf);
+        for (int g = gb; g < ge; ++g) leaf_test_generic(sc, sc.gleaf[g], o, d, time, closest, best);
+    });
 }
 
 // One non-BVH group of hit-obj-list (geometry.scm:33-50): its primitives in
@@ -1677,7 +1667,7 @@ __device__ __forceinline__ void group_closest(const DevScene& sc, const Group& G
                 frac = (time - S.t0) / S.den;
                 last_t0 = S.t0; last_den = S.den; have = true;
             }
-            const v3 cen = mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * frac;
+            const v3 cen = msphere_center(S, frac);
             if constexpr (GEN) sphere_test_tie(sc, o, d, a, ia, cen, S.rr, base + s, closest, best);
             else sphere_test(o, d, a, ia, cen, S.rr, base + s, closest, best);
         }
@@ -1705,6 +1695,8 @@ __device__ __forceinline__ void group_closest(const DevScene& sc, const Group& G
             }
         }
     } else {                                            // geometry.scm:376-431
+        // (restated in list_closest and leaf_test_generic: as one helper k_extend_curves ran 397 -> 377 Mrays/s (curves, 32 spp),
+        // and with the axes chosen per rect k_extend<0> 12 850 -> 12 530 (Cornell): profiles/hit_once/bench_vs_parent.txt)
         // XY: k on z, (a,b) = (x,y); XZ: k on y, (x,z); YZ: k on x, (y,z)
         double ok, dk, oa, da, ob, db;
         if (G.type == LEAF_RECT_XY) { ok = o.z; dk = d.z; oa = o.x; da = d.x; ob = o.y; db = d.y; }
@@ -1754,7 +1746,7 @@ __device__ __forceinline__ void list_closest(const DevScene& sc, const v3 o0, co
             const double a = dot(d, d), ia = 1.0 / a;
             const MSphereRec S = sc.msph[s];
             const double frac = (time - S.t0) / S.den;
-            const v3 cen = mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * frac;
+            const v3 cen = msphere_center(S, frac);
             sphere_test(o, d, a, ia, cen, S.rr, id, closest, best);
         } else if (type == LEAF_KLEIN) {
             if (MED) {
@@ -2046,21 +2038,26 @@ __global__ __launch_bounds__(256) void k_extend(const DevScene sc, const RenderP
 // not on the render path.  Scenes with media are refused by the host (the
 // medium's hit test draws from the path's random stream).
 // =====================================================================
+// the probes' body: ray k's closest hit, with the path's random stream (g) or without one
 template <int F>
-__global__ __launch_bounds__(256) void k_hit_rays(const DevScene sc, const double* __restrict__ rays, uint32_t n,
-                                                  double* __restrict__ out_t, int32_t* __restrict__ out_mat) {
+__device__ __forceinline__ void hit_rays_body(const DevScene& sc, const double* __restrict__ rays, const uint32_t k,
+                                              Rng* g, double* __restrict__ out_t, int32_t* __restrict__ out_mat) {
     extern __shared__ uint32_t s_lstack[];
     constexpr bool BEZ = (F & kFeatCurves) != 0;
     __shared__ BezWave s_bw[BEZ ? 4 : 1];
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    if (k >= n) return;
     const double* r = rays + 7 * (size_t)k;
     double t = 0.0;
     const int32_t leaf = closest_hit<F>(sc, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), r[6], t,
                                         s_lstack + threadIdx.x, sc.lane_stack, &s_bw[BEZ ? (threadIdx.x >> 6) : 0],
-                                        nullptr, tree0_hbm(sc), treeA_hbm(sc));
+                                        g, tree0_hbm(sc), treeA_hbm(sc));
     out_t[k] = leaf < 0 ? 0.0 : t;
     out_mat[k] = leaf < 0 ? -1 : sc.leaves[leaf].mat;
+}
+template <int F>
+__global__ __launch_bounds__(256) void k_hit_rays(const DevScene sc, const double* __restrict__ rays, uint32_t n,
+                                                  double* __restrict__ out_t, int32_t* __restrict__ out_mat) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < n) hit_rays_body<F>(sc, rays, k, nullptr, out_t, out_mat);
 }
 
 // k_hit_rays with the path's random stream (rt_hit_rays_stream): ray k carries the stream of (seed, pixel k,
@@ -2071,20 +2068,11 @@ template <int F>
 __global__ __launch_bounds__(256) void k_hit_rays_stream(const DevScene sc, const double* __restrict__ rays, uint32_t n,
                                                          const uint32_t k0, const uint32_t k1, double* __restrict__ out_t,
                                                          int32_t* __restrict__ out_mat, int32_t* __restrict__ out_draws) {
-    extern __shared__ uint32_t s_lstack[];
-    constexpr bool BEZ = (F & kFeatCurves) != 0;
-    __shared__ BezWave s_bw[BEZ ? 4 : 1];
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k >= n) return;
-    const double* r = rays + 7 * (size_t)k;
-    double t = 0.0;
     Rng g;
     g.init(k0, k1, k, 0u, 0u);
-    const int32_t leaf = closest_hit<F>(sc, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), r[6], t,
-                                        s_lstack + threadIdx.x, sc.lane_stack, &s_bw[BEZ ? (threadIdx.x >> 6) : 0],
-                                        &g, tree0_hbm(sc), treeA_hbm(sc));
-    out_t[k] = leaf < 0 ? 0.0 : t;
-    out_mat[k] = leaf < 0 ? -1 : sc.leaves[leaf].mat;
+    hit_rays_body<F>(sc, rays, k, &g, out_t, out_mat);
     out_draws[k] = (int32_t)g.ctr;
 }
 
@@ -2572,31 +2560,54 @@ __device__ __forceinline__ uint32_t ext_append(const int cls, uint32_t* __restri
     return wave_append(cls, blockIdx.x & (uint32_t)(kShards - 1), counts, shard_cap);
 }
 
-// Dynamic LDS the persistent kernels carve (host and device use the same
-// formula: the kernels check it against the allocation they were given).
-// Layout: tree nodes | leaves | sphere records [| moving spheres] | 16-bit
-// lane stacks | fsph -> leaf id (time-0 tree) | leaf -> material class (bytes).
-__host__ __device__ __forceinline__ size_t lds_tail_bytes(const DevScene& sc) {
-    return ((size_t)sc.n_fsph * 4 + 15) / 16 * 16 + ((size_t)sc.n_leaves + 15) / 16 * 16;
-}
-// time-0 leaf records the LDS kernels stage: none for SOLO scenes (direct leaves)
-__host__ __device__ __forceinline__ int tree0_lds_leaves(const DevScene& sc) { return sc.bvh_solo ? 0 : sc.n_fbleaf; }
-__host__ __device__ __forceinline__ size_t extend_lds_need(const DevScene& sc) {
-    return (size_t)sc.n_fbvh2 * sizeof(BvhNode2) + (size_t)tree0_lds_leaves(sc) * sizeof(BvhLeaf) +
-           (size_t)sc.n_fsph * sizeof(SphereRec) +
-           (size_t)kExtLdsBlock * (size_t)(sc.lane_stack > 0 ? sc.lane_stack : 1) * sizeof(uint16_t) +
-           lds_tail_bytes(sc);
-}
-__host__ __device__ __forceinline__ size_t camera_lds_need(const DevScene& sc) {     // all-times tree
-    return (size_t)sc.n_bvh2 * sizeof(BvhNode2) + (size_t)sc.n_bleaf * sizeof(BvhLeaf) +
-           (size_t)sc.n_sph * sizeof(SphereRec) + (size_t)sc.n_msph * sizeof(MSphereRec) +
-           (size_t)kExtLdsBlock * (size_t)(sc.lane_stack > 0 ? sc.lane_stack : 1) * sizeof(uint16_t) +
-           lds_tail_bytes(sc);
-}
 // stage n 32-bit words (fid, packed class bytes)
 __device__ __forceinline__ void stage_words(uint32_t* dst, const uint32_t* src, const int n, const int nthreads) {
     for (int k = threadIdx.x; k < n; k += nthreads) dst[k] = src[k];
 }
+// The tree a persistent kernel stages in dynamic LDS, stated once for host and device (the kernels check
+// bytes() against the allocation they were given).  all: the all-times tree (k_camera in scenes with
+// moving spheres), else the time-0 tree; solo: DevScene::bvh_solo, direct leaves, so no leaf records.
+// Layout: tree nodes | leaves | sphere records [| moving spheres] | 16-bit lane stacks (kExtLdsBlock lanes) |
+// fsph -> leaf id (time-0 tree) | leaf -> material class (bytes).  The records come first and are whole
+// 16-B words, so a kernel with another stack (k_finish) carves them alone, at its own offset.
+struct LdsTree {
+    bool all;
+    int nn, nl, ns, nm, nf, ncls, stack;     // nodes, leaves, spheres, moving spheres, fid words, class bytes, stack entries
+    __host__ __device__ __forceinline__ LdsTree(const DevScene& sc, const bool all_, const bool solo)
+        : all(all_), nn(all_ ? sc.n_bvh2 : sc.n_fbvh2), nl(all_ ? sc.n_bleaf : (solo ? 0 : sc.n_fbleaf)),
+          ns(all_ ? sc.n_sph : sc.n_fsph), nm(all_ ? sc.n_msph : 0), nf(sc.n_fsph), ncls(sc.n_leaves),
+          stack(kExtLdsBlock * (sc.lane_stack > 0 ? sc.lane_stack : 1)) {}
+    __host__ __device__ __forceinline__ size_t record_bytes() const {
+        return (size_t)nn * sizeof(BvhNode2) + (size_t)nl * sizeof(BvhLeaf) + (size_t)ns * sizeof(SphereRec) +
+               (size_t)nm * sizeof(MSphereRec);
+    }
+    __host__ __device__ __forceinline__ size_t fid_bytes() const { return ((size_t)nf * 4 + 15) / 16 * 16; }
+    __host__ __device__ __forceinline__ size_t bytes() const {
+        return record_bytes() + (size_t)stack * sizeof(uint16_t) + fid_bytes() + ((size_t)ncls + 15) / 16 * 16;
+    }
+    // the carve at `base` (16-B aligned)
+    __device__ __forceinline__ BvhNode2* nodes(void* base) const { return reinterpret_cast<BvhNode2*>(base); }
+    __device__ __forceinline__ BvhLeaf* leaves(void* base) const { return reinterpret_cast<BvhLeaf*>(nodes(base) + nn); }
+    __device__ __forceinline__ SphereRec* sph(void* base) const { return reinterpret_cast<SphereRec*>(leaves(base) + nl); }
+    __device__ __forceinline__ MSphereRec* msph(void* base) const { return reinterpret_cast<MSphereRec*>(sph(base) + ns); }
+    __device__ __forceinline__ uint16_t* lstack(void* base) const { return reinterpret_cast<uint16_t*>(msph(base) + nm); }
+    __device__ __forceinline__ int32_t* fid(void* base) const { return reinterpret_cast<int32_t*>(lstack(base) + stack); }
+    __device__ __forceinline__ uint8_t* cls(void* base) const { return reinterpret_cast<uint8_t*>(fid(base)) + fid_bytes(); }
+    // all threads of the block copy the records (and, with `maps`, fid; with `classes`, the class bytes)
+    __device__ __forceinline__ void stage(void* base, const DevScene& sc, const int nthreads, const bool maps,
+                                          const bool classes) const {
+        stage_lds(nodes(base), all ? sc.bvh2 : sc.fbvh2, nn, nthreads);
+        if (nl) stage_lds(leaves(base), all ? sc.bleaf : sc.fbleaf, nl, nthreads);
+        stage_lds(sph(base), all ? sc.sph : sc.fsph, ns, nthreads);
+        if (all) stage_lds(msph(base), sc.msph, nm, nthreads);
+        if (maps) stage_words(reinterpret_cast<uint32_t*>(fid(base)), reinterpret_cast<const uint32_t*>(sc.fid), nf, nthreads);
+        if (classes) stage_words(reinterpret_cast<uint32_t*>(cls(base)), reinterpret_cast<const uint32_t*>(sc.leaf_cls),
+                                 (ncls + 3) / 4, nthreads);
+    }
+    // the staged tree as the walks take it: the time-0 tree (!all) or the all-times tree (all)
+    __device__ __forceinline__ Tree0 tree0(void* base) const { return Tree0{nodes(base), leaves(base), sph(base), fid(base)}; }
+    __device__ __forceinline__ TreeA treeA(void* base) const { return TreeA{nodes(base), leaves(base), sph(base), msph(base)}; }
+};
 
 // =====================================================================
 // k_extend_lds — k_extend for launches whose rays all carry time +0.0 (every
@@ -2614,25 +2625,16 @@ __global__ __launch_bounds__(kExtLdsBlock, kExtLdsWaves) void k_extend_lds(const
                                                              unsigned long long* __restrict__ err) {
     extern __shared__ uint4 s_dyn[];
     __shared__ uint32_t s_cnt[4 * 16 + 4];
-    const int nn = sc.n_fbvh2, nl = SOLO ? 0 : sc.n_fbleaf, ns = sc.n_fsph;
-    if (extend_lds_need(sc) > lds_bytes || (SOLO && !sc.bvh_solo)) {            // the carve below would leave the allocation
+    const LdsTree lt(sc, false, SOLO);
+    if (lt.bytes() > lds_bytes || (SOLO && !sc.bvh_solo)) {                     // the carve would leave the allocation
         if (threadIdx.x == 0) { atomicOr(err, 1ull); raise_fault(RT_FAULT_LDS); }
         return;
     }
-    BvhNode2* s_nodes = reinterpret_cast<BvhNode2*>(s_dyn);
-    BvhLeaf* s_leaves = reinterpret_cast<BvhLeaf*>(s_nodes + nn);
-    SphereRec* s_sph = reinterpret_cast<SphereRec*>(s_leaves + nl);
-    uint16_t* s_lstack = reinterpret_cast<uint16_t*>(s_sph + ns);
-    int32_t* s_fid = reinterpret_cast<int32_t*>(s_lstack + (size_t)kExtLdsBlock * (sc.lane_stack > 0 ? sc.lane_stack : 1));
-    uint8_t* s_cls = reinterpret_cast<uint8_t*>(s_fid) + ((size_t)ns * 4 + 15) / 16 * 16;
-    stage_lds(s_nodes, sc.fbvh2, nn, kExtLdsBlock);      // the time-0 tree
-    if (!SOLO) stage_lds(s_leaves, sc.fbleaf, nl, kExtLdsBlock);
-    stage_lds(s_sph, sc.fsph, ns, kExtLdsBlock);
-    stage_words(reinterpret_cast<uint32_t*>(s_fid), reinterpret_cast<const uint32_t*>(sc.fid), ns, kExtLdsBlock);
-    stage_words(reinterpret_cast<uint32_t*>(s_cls), reinterpret_cast<const uint32_t*>(sc.leaf_cls),
-                (sc.n_leaves + 3) / 4, kExtLdsBlock);
+    lt.stage(s_dyn, sc, kExtLdsBlock, true, true);         // the time-0 tree
     __syncthreads();
-    const Tree0 t0{s_nodes, s_leaves, s_sph, s_fid};
+    uint16_t* s_lstack = lt.lstack(s_dyn);
+    const uint8_t* s_cls = lt.cls(s_dyn);
+    const Tree0 t0 = lt.tree0(s_dyn);
     const int LS = sc.lane_stack;
     const QMap qm = qmap(in);
     for (uint32_t base = ext_first(); base < n; base += gridDim.x * kExtLdsBlock) {
@@ -2677,29 +2679,17 @@ __global__ __launch_bounds__(kExtLdsBlock, kCameraWaves) void k_camera(const Dev
                                                                           unsigned long long* __restrict__ err) {
     extern __shared__ uint4 s_dyn[];
     __shared__ uint32_t s_cnt[4 * 16 + 4];
-    if ((ALL ? camera_lds_need(sc) : extend_lds_need(sc)) > lds_bytes || (SOLO && !sc.bvh_solo)) {
+    const LdsTree lt(sc, ALL, SOLO);
+    if (lt.bytes() > lds_bytes || (SOLO && !sc.bvh_solo)) {
         if (threadIdx.x == 0) { atomicOr(err, 2ull); raise_fault(RT_FAULT_LDS); }
         return;
     }
-    const int nn = ALL ? sc.n_bvh2 : sc.n_fbvh2, nl = ALL ? sc.n_bleaf : (SOLO ? 0 : sc.n_fbleaf);
-    const int ns = ALL ? sc.n_sph : sc.n_fsph, nm = ALL ? sc.n_msph : 0;
-    BvhNode2* s_nodes = reinterpret_cast<BvhNode2*>(s_dyn);
-    BvhLeaf* s_leaves = reinterpret_cast<BvhLeaf*>(s_nodes + nn);
-    SphereRec* s_sph = reinterpret_cast<SphereRec*>(s_leaves + nl);
-    MSphereRec* s_msph = reinterpret_cast<MSphereRec*>(s_sph + ns);
-    uint16_t* s_lstack = reinterpret_cast<uint16_t*>(s_msph + nm);
-    int32_t* s_fid = reinterpret_cast<int32_t*>(s_lstack + (size_t)kExtLdsBlock * (sc.lane_stack > 0 ? sc.lane_stack : 1));
-    uint8_t* s_cls = reinterpret_cast<uint8_t*>(s_fid) + ((size_t)sc.n_fsph * 4 + 15) / 16 * 16;
-    stage_lds(s_nodes, ALL ? sc.bvh2 : sc.fbvh2, nn, kExtLdsBlock);
-    if (nl) stage_lds(s_leaves, ALL ? sc.bleaf : sc.fbleaf, nl, kExtLdsBlock);
-    stage_lds(s_sph, ALL ? sc.sph : sc.fsph, ns, kExtLdsBlock);
-    if (ALL) stage_lds(s_msph, sc.msph, nm, kExtLdsBlock);
-    stage_words(reinterpret_cast<uint32_t*>(s_fid), reinterpret_cast<const uint32_t*>(sc.fid), sc.n_fsph, kExtLdsBlock);
-    stage_words(reinterpret_cast<uint32_t*>(s_cls), reinterpret_cast<const uint32_t*>(sc.leaf_cls),
-                (sc.n_leaves + 3) / 4, kExtLdsBlock);
+    lt.stage(s_dyn, sc, kExtLdsBlock, true, true);
     __syncthreads();
-    const Tree0 t0 = ALL ? tree0_hbm(sc) : Tree0{s_nodes, s_leaves, s_sph, s_fid};
-    const TreeA ta = ALL ? TreeA{s_nodes, s_leaves, s_sph, s_msph} : treeA_hbm(sc);
+    uint16_t* s_lstack = lt.lstack(s_dyn);
+    const uint8_t* s_cls = lt.cls(s_dyn);
+    const Tree0 t0 = ALL ? tree0_hbm(sc) : lt.tree0(s_dyn);
+    const TreeA ta = ALL ? lt.treeA(s_dyn) : treeA_hbm(sc);
     const int LS = sc.lane_stack;
     for (uint32_t base = ext_first(); base < n; base += gridDim.x * kExtLdsBlock) {
         const uint32_t w = base + ext_lid();
@@ -2731,10 +2721,8 @@ __global__ __launch_bounds__(kExtLdsBlock, kCameraWaves) void k_camera(const Dev
 // =====================================================================
 // k_hit_rays_lds — k_hit_rays (rt_hit_rays_walk) through the LDS kernels'
 // walks: the same closest_hit_lds on a caller's rays, over a tree staged as
-// those kernels stage it (the carve is k_camera's, which for !ALL is
-// k_extend_lds's: nodes | leaves (none for SOLO) | sphere records [| moving
-// spheres] | 16-bit lane stacks | fid), with their block size and register
-// budget.  TIME0: k_extend_lds's query — the time-0 tree in LDS, the all-times
+// those kernels stage it (LdsTree, the one carve all three use), with their
+// block size and register budget.  TIME0: k_extend_lds's query — the time-0 tree in LDS, the all-times
 // tree in HBM, time the literal +0.0 (the host refuses other times).
 // Otherwise k_camera<ALL, SOLO>'s query with the ray's own time.  A test
 // probe, not on the render path; it sits here, after the definitions it
@@ -2746,26 +2734,16 @@ void k_hit_rays_lds(const DevScene sc, const double* __restrict__ rays, const ui
                     int32_t* __restrict__ out_mat, const uint32_t lds_bytes) {
     static_assert(!(TIME0 && ALL), "k_extend_lds stages the time-0 tree only");
     extern __shared__ uint4 s_dyn[];
-    if ((ALL ? camera_lds_need(sc) : extend_lds_need(sc)) > lds_bytes || (SOLO && !sc.bvh_solo)) {
-        if (threadIdx.x == 0) raise_fault(RT_FAULT_LDS);     // the carve below would leave the allocation
+    const LdsTree lt(sc, ALL, SOLO);
+    if (lt.bytes() > lds_bytes || (SOLO && !sc.bvh_solo)) {
+        if (threadIdx.x == 0) raise_fault(RT_FAULT_LDS);     // the carve would leave the allocation
         return;
     }
-    const int nn = ALL ? sc.n_bvh2 : sc.n_fbvh2, nl = ALL ? sc.n_bleaf : (SOLO ? 0 : sc.n_fbleaf);
-    const int ns = ALL ? sc.n_sph : sc.n_fsph, nm = ALL ? sc.n_msph : 0;
-    BvhNode2* s_nodes = reinterpret_cast<BvhNode2*>(s_dyn);
-    BvhLeaf* s_leaves = reinterpret_cast<BvhLeaf*>(s_nodes + nn);
-    SphereRec* s_sph = reinterpret_cast<SphereRec*>(s_leaves + nl);
-    MSphereRec* s_msph = reinterpret_cast<MSphereRec*>(s_sph + ns);
-    uint16_t* s_lstack = reinterpret_cast<uint16_t*>(s_msph + nm);
-    int32_t* s_fid = reinterpret_cast<int32_t*>(s_lstack + (size_t)kExtLdsBlock * (sc.lane_stack > 0 ? sc.lane_stack : 1));
-    stage_lds(s_nodes, ALL ? sc.bvh2 : sc.fbvh2, nn, kExtLdsBlock);
-    if (nl) stage_lds(s_leaves, ALL ? sc.bleaf : sc.fbleaf, nl, kExtLdsBlock);
-    stage_lds(s_sph, ALL ? sc.sph : sc.fsph, ns, kExtLdsBlock);
-    if (ALL) stage_lds(s_msph, sc.msph, nm, kExtLdsBlock);
-    stage_words(reinterpret_cast<uint32_t*>(s_fid), reinterpret_cast<const uint32_t*>(sc.fid), sc.n_fsph, kExtLdsBlock);
+    lt.stage(s_dyn, sc, kExtLdsBlock, true, false);        // (no hit queues here: the class bytes stay unstaged)
     __syncthreads();
-    const Tree0 t0 = ALL ? tree0_hbm(sc) : Tree0{s_nodes, s_leaves, s_sph, s_fid};
-    const TreeA ta = ALL ? TreeA{s_nodes, s_leaves, s_sph, s_msph} : treeA_hbm(sc);
+    uint16_t* s_lstack = lt.lstack(s_dyn);
+    const Tree0 t0 = ALL ? tree0_hbm(sc) : lt.tree0(s_dyn);
+    const TreeA ta = ALL ? lt.treeA(s_dyn) : treeA_hbm(sc);
     const int LS = sc.lane_stack;
     for (uint32_t base = ext_first(); base < n; base += gridDim.x * kExtLdsBlock) {
         const uint32_t k = base + ext_lid();
@@ -3015,6 +2993,45 @@ __device__ __forceinline__ v3 light_random(const DevLight& L, const v3 o, Rng& g
 }
 
 // ------------------------------------------------------------- shading
+// The hit record (material.scm's hit-record, before the material's scatter): the point on the (instance-local)
+// ray, the normal by leaf type, the record's u and v, the flip, and both taken back out of the instance
+// chain, not renormalised.  shade_hit (every shade kernel and the tail) and k_features form it here.
+template <int TL>
+__device__ __forceinline__ void hit_record(const DevScene& sc, const LeafInfo& li, const v3 o0, const v3 d0,
+                                           const double time, const double t, v3& pt, v3& nrm, double& tu, double& tv) {
+    v3 o = o0, d = d0;
+    if (li.chain >= 0) chain_ray(sc.chains[li.chain], o, d);
+    pt = o + d * t;                            // point-at-parameter on the (local) ray
+    if (li.type == LEAF_SPHERE) {
+        nrm = (pt - mk(li.c[0], li.c[1], li.c[2])) * li.inv_r;
+    } else if (li.type == LEAF_MSPHERE) {
+        v3 cen;
+        if (__double_as_longlong(time) == 0ll) {            // center(0), computed as below on the host
+            cen = mk(li.c[0], li.c[1], li.c[2]);
+        } else {
+            const MSphereRec S = sc.msph[li.local];
+            cen = msphere_center(S, (time - S.t0) / S.den);
+        }
+        nrm = (pt - cen) * li.inv_r;
+    } else if (li.type == LEAF_RECT_XY) {
+        nrm = mk(0.0, 0.0, 1.0);
+    } else if (li.type == LEAF_RECT_XZ) {
+        nrm = mk(0.0, 1.0, 0.0);
+    } else if (li.type == LEAF_RECT_YZ || li.type == LEAF_MEDIUM) {
+        nrm = mk(1.0, 0.0, 0.0);                             // medium: (v:vec3 1 0 0), geometry.scm:569
+    } else if (li.type == LEAF_KLEIN) {
+        const KleinRec K = sc.klein[li.local];
+        nrm = klein_normal(mk(K.cx, K.cy, K.cz), pt);        // at ray-pos = point-at-parameter, :664
+    } else {
+        nrm = d * -1.0;                                      // curve: (v:scale (dir r) -1), bezier.scm:204
+    }
+    tu = 0.0; tv = 0.0;                                      // the record's u, v: read by image textures only
+    if constexpr (TL >= kTexImage) {
+        if (li.tex_kind == TK_GENERIC) hit_uv(sc, li, pt, nrm, tu, tv);
+    }
+    if (li.flip) nrm = nrm * -1.0;                          // flip-normals :438
+    if (li.chain >= 0) chain_hit(sc.chains[li.chain], pt, nrm);
+}
 // Hit record + material (material.scm:15-111).  MATF = the material type a
 // queue holds (compile-time; -1 = any, used by the tail kernel).  Returns true
 // if the path continues (p holds the scattered ray, new throughput, depth+1);
@@ -3031,39 +3048,9 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
                                           const double* __restrict__ trig = rtlibm::kSinCosTab) {
     L = mk(0.0, 0.0, 0.0);
     const LeafInfo& li = leaves[leaf];                       // one record: geometry, material, texture (fields read where used)
-    v3 o = p.o, d = p.d;
-    if (li.chain >= 0) chain_ray(sc.chains[li.chain], o, d);
-    v3 pt = o + d * t;                         // point-at-parameter on the (local) ray
-    v3 nrm;
-    if (li.type == LEAF_SPHERE) {
-        nrm = (pt - mk(li.c[0], li.c[1], li.c[2])) * li.inv_r;
-    } else if (li.type == LEAF_MSPHERE) {
-        v3 cen;
-        if (__double_as_longlong(p.time) == 0ll) {          // center(0), computed as below on the host
-            cen = mk(li.c[0], li.c[1], li.c[2]);
-        } else {
-            const MSphereRec S = sc.msph[li.local];
-            cen = mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * ((p.time - S.t0) / S.den);
-        }
-        nrm = (pt - cen) * li.inv_r;
-    } else if (li.type == LEAF_RECT_XY) {
-        nrm = mk(0.0, 0.0, 1.0);
-    } else if (li.type == LEAF_RECT_XZ) {
-        nrm = mk(0.0, 1.0, 0.0);
-    } else if (li.type == LEAF_RECT_YZ || li.type == LEAF_MEDIUM) {
-        nrm = mk(1.0, 0.0, 0.0);                             // medium: (v:vec3 1 0 0), geometry.scm:569
-    } else if (li.type == LEAF_KLEIN) {
-        const KleinRec K = sc.klein[li.local];
-        nrm = klein_normal(mk(K.cx, K.cy, K.cz), pt);        // at ray-pos = point-at-parameter, :664
-    } else {
-        nrm = d * -1.0;                                      // curve: (v:scale (dir r) -1), bezier.scm:204
-    }
-    double tu = 0.0, tv = 0.0;                               // the record's u, v: read by image textures only
-    if constexpr (TL >= kTexImage) {
-        if (li.tex_kind == TK_GENERIC) hit_uv(sc, li, pt, nrm, tu, tv);
-    }
-    if (li.flip) nrm = nrm * -1.0;                          // flip-normals :438
-    if (li.chain >= 0) chain_hit(sc.chains[li.chain], pt, nrm);
+    v3 pt, nrm;
+    double tu, tv;
+    hit_record<TL>(sc, li, p.o, p.d, p.time, t, pt, nrm, tu, tv);
     const int mt = (MATF >= 0) ? MATF : li.mtype;
     const v3 rdir = p.d;
     const bool can_continue = p.depth < (uint32_t)kMaxDepth;
@@ -3285,20 +3272,14 @@ __global__ __launch_bounds__(256, (finish_waves<F, TL, LSM>())) void k_finish(co
     __shared__ BezWave s_bw[BEZ ? 4 : 1];
     const int words = SOLO ? (256 * (LS > 0 ? LS : 1) * 2 + 15) / 16            // stack size in uint4
                            : (256 * (LS > 0 ? LS : 1) + 3) / 4;
-    const int tl_leaves = SOLO ? 0 : sc.n_fbleaf;
-    const size_t tree_words = tree0_lds ? ((size_t)sc.n_fbvh2 * sizeof(BvhNode2) + (size_t)tl_leaves * sizeof(BvhLeaf) +
-                                           (size_t)sc.n_fsph * sizeof(SphereRec)) / 16 : 0;
+    // this kernel's own placement: its 256-lane stack first, then LdsTree's records alone (fid stays in HBM)
+    const LdsTree lt(sc, false, SOLO);
+    const size_t tree_words = tree0_lds ? lt.record_bytes() / 16 : 0;
     PerlinLds& P = *reinterpret_cast<PerlinLds*>(s_fdyn + words + tree_words);
     Tree0 t0 = tree0_hbm(sc);
     if (tree0_lds) {
-        const int nn = sc.n_fbvh2, nl = tl_leaves, ns = sc.n_fsph;
-        BvhNode2* s_nodes = reinterpret_cast<BvhNode2*>(s_fdyn + words);
-        BvhLeaf* s_leaves = reinterpret_cast<BvhLeaf*>(s_nodes + nn);
-        SphereRec* s_sph = reinterpret_cast<SphereRec*>(s_leaves + nl);
-        stage_lds(s_nodes, sc.fbvh2, nn, 256);
-        if (!SOLO) stage_lds(s_leaves, sc.fbleaf, nl, 256);
-        stage_lds(s_sph, sc.fsph, ns, 256);
-        t0 = Tree0{s_nodes, s_leaves, s_sph, sc.fid};
+        lt.stage(s_fdyn + words, sc, 256, false, false);
+        t0 = Tree0{lt.nodes(s_fdyn + words), lt.leaves(s_fdyn + words), lt.sph(s_fdyn + words), sc.fid};
         __syncthreads();
     }
     stage_perlin<TL>(sc, P);
@@ -3363,45 +3344,6 @@ __global__ __launch_bounds__(256, (finish_waves<F, TL, LSM>())) void k_finish(co
 // (seed, pixel, pass) — camera_ray, the same draws — and its closest hit with the generic closest_hit<F>
 // (a medium's hit test goes on drawing from the ray's stream, as k_extend's does at depth 0).
 // =====================================================================
-// The hit record as shade_hit forms it before the material's scatter: the point on the (instance-local)
-// ray and the normal, flipped and taken back out of the instance chain, not renormalised.  Restated here:
-// shade_hit's own copy is scheduled into every shade kernel's register budget.
-template <int TL>
-__device__ __forceinline__ void feature_hit(const DevScene& sc, const LeafInfo& li, const v3 o0, const v3 d0,
-                                            const double time, const double t, v3& pt, v3& nrm, double& tu, double& tv) {
-    v3 o = o0, d = d0;
-    if (li.chain >= 0) chain_ray(sc.chains[li.chain], o, d);
-    pt = o + d * t;
-    if (li.type == LEAF_SPHERE) {
-        nrm = (pt - mk(li.c[0], li.c[1], li.c[2])) * li.inv_r;
-    } else if (li.type == LEAF_MSPHERE) {
-        v3 cen;
-        if (__double_as_longlong(time) == 0ll) {
-            cen = mk(li.c[0], li.c[1], li.c[2]);
-        } else {
-            const MSphereRec S = sc.msph[li.local];
-            cen = mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * ((time - S.t0) / S.den);
-        }
-        nrm = (pt - cen) * li.inv_r;
-    } else if (li.type == LEAF_RECT_XY) {
-        nrm = mk(0.0, 0.0, 1.0);
-    } else if (li.type == LEAF_RECT_XZ) {
-        nrm = mk(0.0, 1.0, 0.0);
-    } else if (li.type == LEAF_RECT_YZ || li.type == LEAF_MEDIUM) {
-        nrm = mk(1.0, 0.0, 0.0);
-    } else if (li.type == LEAF_KLEIN) {
-        const KleinRec K = sc.klein[li.local];
-        nrm = klein_normal(mk(K.cx, K.cy, K.cz), pt);
-    } else {
-        nrm = d * -1.0;
-    }
-    tu = 0.0; tv = 0.0;
-    if constexpr (TL >= kTexImage) {
-        if (li.tex_kind == TK_GENERIC) hit_uv(sc, li, pt, nrm, tu, tv);
-    }
-    if (li.flip) nrm = nrm * -1.0;
-    if (li.chain >= 0) chain_hit(sc.chains[li.chain], pt, nrm);
-}
 template <int F, int TL>
 __global__ __launch_bounds__(256) void k_features(const DevScene sc, const RenderParams rp, const uint32_t S,
                                                   double* __restrict__ feat) {
@@ -3433,7 +3375,7 @@ __global__ __launch_bounds__(256) void k_features(const DevScene sc, const Rende
             const LeafInfo& li = sc.leaves[leaf];
             v3 pt;
             double tu, tv;
-            feature_hit<TL>(sc, li, o, d, time, t, pt, n, tu, tv);
+            hit_record<TL>(sc, li, o, d, time, t, pt, n, tu, tv);
             a = li.mtype == MAT_DIELECTRIC ? mk(1.0, 1.0, 1.0) : leaf_tex<TL>(sc, P, li, pt, tu, tv);
             tt = t;
             hit = 1.0;
@@ -3458,10 +3400,13 @@ static bool finish_generic() {               // RTAMD_FINISH_GENERIC: the group-
     const char* e = std::getenv("RTAMD_FINISH_GENERIC");  // read per launch: tests switch it inside one process
     return e != nullptr && e[0] != '0';
 }
-static int scene_features(const DevScene& sc) {
+// A scene's closest-hit feature set: one of the six legal ones (0, kFeatCurves, kFeatExtra, both, kFeatGeneric,
+// kFeatGeneric | kFeatExtra), which dispatch below enumerates
+struct FeatSet { int f; };
+static FeatSet scene_features(const DevScene& sc) {
     // (build_scene: generic leaves never with curves or Klein sets; with media only in a media forest)
-    if (sc.n_gleaf > 0) return sc.n_med > 0 ? kFeatGeneric | kFeatExtra : kFeatGeneric;
-    return (sc.n_bez > 0 ? kFeatCurves : 0) | (sc.n_med > 0 || sc.n_klein > 0 ? kFeatExtra : 0);
+    if (sc.n_gleaf > 0) return FeatSet{sc.n_med > 0 ? kFeatGeneric | kFeatExtra : kFeatGeneric};
+    return FeatSet{(sc.n_bez > 0 ? kFeatCurves : 0) | (sc.n_med > 0 || sc.n_klein > 0 ? kFeatExtra : 0)};
 }
 static int scene_tex_level(const DevScene& sc) {     // the instances a scene's launches take
     return sc.has_image_tex ? kTexImage : sc.has_noise_tex ? kTexPerlin : kTexPlain;
@@ -3481,10 +3426,11 @@ static uint32_t shard_blocks(const uint32_t blocks) { return (blocks + kShards -
 // Kernel selection.  Every instance of a kernel template has one signature, so a family's selector maps the
 // run-time facts to a typed pointer, and that pointer is what the launch, hipFuncSetAttribute, the occupancy
 // query and its cache key all use.  Only the instances a selector names are compiled.
-// dispatch(f, a, b, ...): f(A, B, ...) with each run-time bool or UpTo as a std::integral_constant
+// dispatch(f, a, b, ...): f(A, B, ...) with each run-time bool, UpTo or FeatSet as a std::integral_constant
 template <int N> struct UpTo { int v; };     // an int in 0 .. N for dispatch (anything above counts as N)
 template <class Fn> static auto dispatch(Fn&& f) { return f(); }
 template <class Fn, int N, class... Rest> static auto dispatch(Fn&& f, UpTo<N> v, Rest... rest);
+template <class Fn, class... Rest> static auto dispatch(Fn&& f, FeatSet v, Rest... rest);
 template <class Fn, class... Rest>
 static auto dispatch(Fn&& f, bool b, Rest... rest) {
     return b ? dispatch([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
@@ -3494,6 +3440,21 @@ template <class Fn, int N, class... Rest>
 static auto dispatch(Fn&& f, UpTo<N> v, Rest... rest) {
     if constexpr (N > 0) if (v.v < N) return dispatch(f, UpTo<N - 1>{v.v}, rest...);
     return dispatch([&](auto... c) { return f(std::integral_constant<int, N>{}, c...); }, rest...);
+}
+template <class Fn, class... Rest>
+static auto dispatch(Fn&& f, FeatSet v, Rest... rest) {
+    const auto at = [&](auto F) { return dispatch([&](auto... c) { return f(F, c...); }, rest...); };
+    switch (v.f) {
+    case kFeatCurves: return at(std::integral_constant<int, kFeatCurves>{});
+    case kFeatExtra: return at(std::integral_constant<int, kFeatExtra>{});
+    case kFeatCurves | kFeatExtra: return at(std::integral_constant<int, kFeatCurves | kFeatExtra>{});
+    case kFeatGeneric: return at(std::integral_constant<int, kFeatGeneric>{});
+    case kFeatGeneric | kFeatExtra: return at(std::integral_constant<int, kFeatGeneric | kFeatExtra>{});
+    case 0: return at(std::integral_constant<int, 0>{});
+    default:                                    // not a set build_scene can produce: no kernel to fall back on
+        std::fprintf(stderr, "rtamd: illegal closest-hit feature set %d\n", v.f);
+        std::abort();
+    }
 }
 using TexLevel = UpTo<kTexImage>;
 using ExtendKernel = void (*)(DevScene, RenderParams, PathState, QView, uint32_t, HitBuf, uint32_t, uint32_t*, bool);
@@ -3512,9 +3473,7 @@ using FinishKernel = void (*)(const DevScene*, RenderParams, PathState, QView, u
                               uint32_t);
 using FeaturesKernel = void (*)(DevScene, RenderParams, uint32_t, double*);
 static ExtendKernel extend_kernel(const DevScene& sc) {
-    if (scene_features(sc) == kFeatGeneric) return k_extend<kFeatGeneric>;
-    if (scene_features(sc) == (kFeatGeneric | kFeatExtra)) return k_extend<kFeatGeneric | kFeatExtra>;
-    return dispatch([](auto F) -> ExtendKernel { return k_extend<F()>; }, UpTo<3>{scene_features(sc)});
+    return dispatch([](auto F) -> ExtendKernel { return k_extend<F()>; }, scene_features(sc));
 }
 // FUSE: 0 one depth, 1 every depth from fuse->depth on with the device libm, 2 with the exact libm
 static CurveKernel curve_kernel(const RenderParams& rp, const CurveFuse* fuse) {
@@ -3529,15 +3488,17 @@ static CameraKernel camera_kernel(const DevScene& sc) {
     return dispatch([](auto ALL, auto SOLO) -> CameraKernel { return k_camera<ALL(), SOLO()>; },
                   !sc.tree0_any_time, sc.bvh_solo != 0);
 }
+// the probes' instances: plain spheres and generic trees (media forests: the stream probe only) take the
+// render's feature set, every other scene the one instance with curves, media and Klein sets
+constexpr int probe_features(const int f, const bool forest) {
+    return (f == 0 || f == kFeatGeneric || (forest && f == (kFeatGeneric | kFeatExtra))) ? f : kFeatCurves | kFeatExtra;
+}
 static HitRaysKernel hit_rays_kernel(const DevScene& sc) {
-    if (scene_features(sc) == kFeatGeneric) return k_hit_rays<kFeatGeneric>;
-    return scene_features(sc) ? k_hit_rays<kFeatCurves | kFeatExtra> : k_hit_rays<0>;
+    return dispatch([](auto F) -> HitRaysKernel { return k_hit_rays<probe_features(F(), false)>; }, scene_features(sc));
 }
 static HitRaysStreamKernel hit_rays_stream_kernel(const DevScene& sc) {
-    const int f = scene_features(sc);
-    if (f == (kFeatGeneric | kFeatExtra)) return k_hit_rays_stream<kFeatGeneric | kFeatExtra>;
-    if (f == kFeatGeneric) return k_hit_rays_stream<kFeatGeneric>;
-    return f ? k_hit_rays_stream<kFeatCurves | kFeatExtra> : k_hit_rays_stream<0>;
+    return dispatch([](auto F) -> HitRaysStreamKernel { return k_hit_rays_stream<probe_features(F(), true)>; },
+                    scene_features(sc));
 }
 // the probe of k_extend_lds's walk (time0) or k_camera's: the instance with that kernel's arguments
 static HitRaysLdsKernel hit_rays_lds_kernel(const DevScene& sc, const bool time0) {
@@ -3568,34 +3529,22 @@ static ShadeKernel shade_kernel(const int mat, const DevScene& sc, const RenderP
 // ones trims its register file
 static int finish_tex_level(const DevScene& sc) {
     const int tl = scene_tex_level(sc);
-    return scene_features(sc) > 0 && tl < kTexPerlin ? kTexPerlin : tl;
+    return scene_features(sc).f > 0 && tl < kTexPerlin ? kTexPerlin : tl;
 }
 static FinishKernel finish_kernel(const DevScene& sc, const RenderParams& rp, const bool solo) {
-    const int f = scene_features(sc), tl = finish_tex_level(sc);
+    const FeatSet f = scene_features(sc);
+    const int tl = finish_tex_level(sc);
     const bool ex = rp.exact_libm != 0;
-    if (f == kFeatGeneric)
-        return dispatch([](auto IMG, auto EX) -> FinishKernel {
-            return k_finish<kFeatGeneric, IMG() ? kTexImage : kTexPerlin, true, false, EX()>;
-        }, tl == kTexImage, ex);
-    if (f == (kFeatGeneric | kFeatExtra))
-        return dispatch([](auto IMG, auto EX) -> FinishKernel {
-            return k_finish<kFeatGeneric | kFeatExtra, IMG() ? kTexImage : kTexPerlin, true, false, EX()>;
-        }, tl == kTexImage, ex);
-    if (f > 0)
-        return dispatch([](auto F1, auto IMG, auto EX) -> FinishKernel {
-            return k_finish<F1() + 1, IMG() ? kTexImage : kTexPerlin, true, false, EX()>;
-        }, UpTo<2>{f - 1}, tl == kTexImage, ex);
+    if (f.f > 0)
+        return dispatch([](auto F, auto IMG, auto EX) -> FinishKernel {
+            return k_finish<F(), IMG() ? kTexImage : kTexPerlin, true, false, EX()>;
+        }, f, tl == kTexImage, ex);
     return dispatch([](auto TL, auto LS, auto SOLO, auto EX) -> FinishKernel { return k_finish<0, TL(), LS(), SOLO(), EX()>; },
                   TexLevel{tl}, sc.light.type != LIGHT_OFF, solo, ex);
 }
 static FeaturesKernel features_kernel(const DevScene& sc) {
-    if (scene_features(sc) == kFeatGeneric)
-        return dispatch([](auto TL) -> FeaturesKernel { return k_features<kFeatGeneric, TL()>; }, TexLevel{scene_tex_level(sc)});
-    if (scene_features(sc) == (kFeatGeneric | kFeatExtra))
-        return dispatch([](auto TL) -> FeaturesKernel { return k_features<kFeatGeneric | kFeatExtra, TL()>; },
-                        TexLevel{scene_tex_level(sc)});
     return dispatch([](auto F, auto TL) -> FeaturesKernel { return k_features<F(), TL()>; },
-                  UpTo<3>{scene_features(sc)}, TexLevel{scene_tex_level(sc)});
+                    scene_features(sc), TexLevel{scene_tex_level(sc)});
 }
 
 // resident blocks of a curve kernel instance for its dynamic LDS, cached per (kernel, device, LDS bytes)
@@ -3621,7 +3570,7 @@ hipError_t launch_extend(const DevScene& sc, const DevScene*, const RenderParams
     const uint32_t blocks = (n + 255u) / 256u;
     // the persistent curve kernel: every curve in the world BVH (its groups outside the BVH are spheres and
     // rects only: group_closest<0>, so the per-lane curve walk is not compiled into it)
-    if (scene_features(sc) == kFeatCurves && sc.bvh_has_bez && sc.bez_groups == 0 && claim && curve_blocks() > 0) {
+    if (scene_features(sc).f == kFeatCurves && sc.bvh_has_bez && sc.bez_groups == 0 && claim && curve_blocks() > 0) {
         // resident blocks only: later blocks would find the rays claimed.  The BVH4 walk's LDS stack column
         // holds lds4 entries per lane (the rest in the overflow area).  Occupancy per (device, LDS bytes)
         const size_t clds = (size_t)256 * (size_t)(sc.lds4 > 0 ? sc.lds4 : 1) * sizeof(uint32_t);
@@ -3671,7 +3620,7 @@ hipError_t launch_features(const DevScene& sc, const RenderParams& rp, uint32_t 
 size_t extend_lds_bytes(const DevScene& sc) {
     if (!sc.fbvh2 || sc.n_bez || sc.n_med || sc.n_klein) return 0;
     if (sc.n_fbvh2 >= 32768 || sc.n_fbleaf >= 32768) return 0;        // 16-bit stack entries
-    return extend_lds_need(sc);
+    return LdsTree(sc, false, sc.bvh_solo != 0).bytes();
 }
 // the grid of a persistent LDS kernel over n items
 static uint32_t lds_grid(const uint32_t n, const uint32_t max_blocks) {
@@ -3706,7 +3655,7 @@ size_t camera_lds_bytes(const DevScene& sc) {
     if (!sc.fbvh2 || sc.n_bez || sc.n_med || sc.n_klein) return 0;
     if (sc.tree0_any_time) return extend_lds_bytes(sc);
     if (sc.n_bvh2 >= 32768 || sc.n_bleaf >= 32768) return 0;          // 16-bit stack entries
-    return camera_lds_need(sc);
+    return LdsTree(sc, true, sc.bvh_solo != 0).bytes();
 }
 hipError_t camera_prepare(const DevScene& sc, size_t lds, uint32_t* max_blocks) {
     return resident_blocks(reinterpret_cast<const void*>(camera_kernel(sc)), lds, max_blocks);
@@ -3756,14 +3705,13 @@ hipError_t launch_finish(const DevScene& sc, const DevScene* scd, const RenderPa
                          hipStream_t s) {
     uint32_t blocks = (n + 255u) / 256u;
     if (blocks > finish_blocks()) blocks = finish_blocks();   // persistent lanes refill from the path list
-    const size_t tree = (size_t)sc.n_fbvh2 * sizeof(BvhNode2) + (size_t)sc.n_fbleaf * sizeof(BvhLeaf) +
-                        (size_t)sc.n_fsph * sizeof(SphereRec);
+    const size_t tree = LdsTree(sc, false, false).record_bytes();
     const int tree0_lds = (sc.fbvh2 && tree0_budget > 0 && tree <= tree0_budget) ? 1 : 0;
     // SOLO tail: plain-sphere world in one BVH, its time-0 tree in LDS, child refs within int16
-    const bool solo = tree0_lds && sc.bvh_solo && scene_features(sc) == 0 && extend_lds_bytes(sc) > 0 &&
+    const bool solo = tree0_lds && sc.bvh_solo && scene_features(sc).f == 0 && extend_lds_bytes(sc) > 0 &&
                       sc.n_bvh2 < 32768 && sc.n_bleaf < 32768 && !finish_generic();
     size_t lds = (lane_stack_lds(sc, solo ? sizeof(uint16_t) : sizeof(uint32_t)) + 15) / 16 * 16;
-    if (tree0_lds) lds += solo ? tree - (size_t)sc.n_fbleaf * sizeof(BvhLeaf) : tree;
+    if (tree0_lds) lds += LdsTree(sc, false, solo).record_bytes();
     // the Perlin tables ride at the end of the dynamic LDS, only where they are staged (TL >= kTexPerlin and tables given)
     if (finish_tex_level(sc) >= kTexPerlin && sc.has_perlin) lds += sizeof(PerlinLds);
     hipLaunchKernelGGL(finish_kernel(sc, rp, solo), dim3(blocks), dim3(256), lds, s, scd, rp, st, in, n, seg_count,
