@@ -398,6 +398,16 @@ typedef struct rt_tree_info {
 #define RT_HAS_GENERIC_BVH 1
 #define RT_HAS_MEDIA_BVH 1
 int rt_get_tree_info(int scene, rt_tree_info* out);
+/* Whether a committed scene's wavefront queues its lambertian hits as point records (the hit
+ * point instead of t, so the lambertian shade gathers no ray): *out = 1 when the scene's world is one sphere
+ * BVH (rt_scene_info.bvh_solo) whose leaves stand under no rt_add_translate / rt_add_rotate_y, at least one
+ * of the persistent LDS kernels runs (extend_lds_bytes or camera_lds_bytes > 0), the scene has no light
+ * sampling target and no image texture, and RTAMD_NO_POINT_HITS is not set in the environment (read per
+ * render and per call here; set, every queue keeps the t records) — else 0.  Images do not depend on it, bit
+ * for bit.  A diagnostic for tests and A/B runs: opt-in, RT_ABI_VERSION stays 7 and rt_scene_info and
+ * rt_stats keep their layouts; test RT_HAS_POINT_HITS for this entry point. */
+#define RT_HAS_POINT_HITS 1
+int rt_scene_point_hits(int scene, int* out);
 /* Record per-kernel HIP events during renders (adds a little host overhead). */
 int rt_set_profiling(int scene, int enabled);
 

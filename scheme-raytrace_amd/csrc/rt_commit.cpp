@@ -198,6 +198,12 @@ int commit_scene(Scene* s, int world) {
     if (!h.bvh4.empty())
         if ((rc = size_curve_buffers(s, d))) return rc;
     prepare_lds(s, d);
+    // point records hold the point on the world ray: right only where hit_record would take no leaf into an
+    // instance chain and the normal needs the point alone (a SOLO world's leaves, checked here all the same)
+    s->point_hits = point_hits_scene(d) && (s->ext_lds || s->cam_lds) &&
+                    std::all_of(h.leaves.begin(), h.leaves.end(), [](const LeafInfo& li) {
+                        return li.chain < 0 && (li.type == LEAF_SPHERE || li.type == LEAF_MSPHERE);
+                    });
     HIPCHK(s->d_dev.ensure(sizeof(DevScene)));
     COMMIT_MARK("upload");
     HIPCHK(hipMemcpy(s->d_dev.p, &d, sizeof(DevScene), hipMemcpyHostToDevice));

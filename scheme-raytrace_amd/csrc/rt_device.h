@@ -264,7 +264,15 @@ struct PathState {
 // kernel reads its queue front to back (no gather of a separate hit array).
 // Queue c starts at h + c * stride.
 struct alignas(16) HitRec { double t; int32_t leaf; uint32_t slot; };
-struct HitBuf { HitRec* h; uint32_t stride; };
+// Point records (the lambertian queue of the SOLO LDS kernels' launches, rt_render.cpp point_hits): the hit
+// point itself, o + d * t as hit_record forms it, instead of t.  The lambertian scatter reads nothing else
+// of the incoming ray, so its shade (k_shade's PT instances) loads no RayRec, and k_camera stores none for
+// these hits.  A launch writes queue 0 in one format or the other; queues 1..3 are always HitRec.
+struct alignas(16) HitPt { double px, py, pz; int32_t leaf; uint32_t slot; };
+static_assert(sizeof(HitPt) == 32, "HitPt layout");
+// hp: queue 0 as point records.  The allocation is 5 * stride 16-B words: hp takes the first two strides,
+// h starts one stride in, so its queue 0 (HitRec launches) lies over hp's second half and queues 1..3 behind it
+struct HitBuf { HitRec* h; uint32_t stride; HitPt* hp; };
 
 // Sharded queues.  Stream compaction appends through one atomic per block
 // and class on a counter chosen by blockIdx % kShards (8 XCDs), so no single

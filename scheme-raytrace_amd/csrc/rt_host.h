@@ -151,6 +151,10 @@ struct Scene : SceneDesc {       // the builder's record (rt_model.h) and what a
     uint32_t ext_lds_blocks = 0;
     size_t cam_lds = 0;                            // k_camera (fused raygen + depth-0 extend), same
     uint32_t cam_blocks = 0;
+    // those two kernels queue lambertian hits as point records (rt_device.h HitPt): a SOLO world whose every
+    // leaf is a sphere or moving sphere under no instance chain, checked at the commit (RTAMD_NO_POINT_HITS,
+    // read per render, switches the records off)
+    bool point_hits = false;
     // render buffers (the lanes' path pools belong to the context)
     DevBuf pixlist;
     int pix_nx = -1, pix_ny = -1, pix_y0 = -1, pix_y1 = -1, pix_shard = -1, pix_nshard = -1;

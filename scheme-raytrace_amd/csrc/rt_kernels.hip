@@ -1873,12 +1873,16 @@ __device__ __forceinline__ void wid_key(const RenderParams& rp, const uint32_t w
 }
 // depth 0: slot i of the raygen output (wid = i, throughput 1); deeper: the
 // path record (its depth is the iteration's, passed in)
+// RAY = false (a point-record queue's shade): the ray record is not read, p.o and p.d are the caller's
+template <bool RAY = true>
 __device__ __forceinline__ void load_path(const PathState& st, uint32_t i, PathRegs& p, const RenderParams& rp,
                                           const uint32_t depth) {
     const bool depth0 = depth == 0u;
-    const RayRec R = st.ray[i];
-    p.o = mk(R.ox, R.oy, R.oz);
-    p.d = mk(R.dx, R.dy, R.dz);
+    if constexpr (RAY) {
+        const RayRec R = st.ray[i];
+        p.o = mk(R.ox, R.oy, R.oz);
+        p.d = mk(R.dx, R.dy, R.dz);
+    }
     if (depth0) {
         p.time = st.tm[i];
         p.T = mk(1.0, 1.0, 1.0);
@@ -2560,6 +2564,21 @@ __device__ __forceinline__ uint32_t ext_append(const int cls, uint32_t* __restri
     return wave_append(cls, blockIdx.x & (uint32_t)(kShards - 1), counts, shard_cap);
 }
 
+// The persistent LDS kernels' hit store.  PT: a lambertian hit goes to queue 0 as a point record (rt_device.h
+// HitPt); hit_point forms the point as hit_record does for a leaf under no instance chain (the build does not
+// contract a * b + c, so the bits are the shade's own) and leaves its x where the record keeps t
+__device__ __forceinline__ void hit_point(const v3 o, const v3 d, const double t, double& px, double& py, double& pz) {
+    const v3 pt = o + d * t;
+    px = pt.x; py = pt.y; pz = pt.z;
+}
+template <bool PT>
+__device__ __forceinline__ void put_hit(const HitBuf& hit, const int cls, const uint32_t slot, const HitRec hr,
+                                        const double py, const double pz) {
+    if (cls < 0 || slot == kNoSlot) return;
+    if (PT && cls == MAT_LAMBERTIAN) hit.hp[slot] = HitPt{hr.t, py, pz, hr.leaf, hr.slot};
+    else hit.h[(size_t)cls * hit.stride + slot] = hr;
+}
+
 // stage n 32-bit words (fid, packed class bytes)
 __device__ __forceinline__ void stage_words(uint32_t* dst, const uint32_t* src, const int n, const int nthreads) {
     for (int k = threadIdx.x; k < n; k += nthreads) dst[k] = src[k];
@@ -2617,7 +2636,10 @@ struct LdsTree {
 // L1/L2 latency.  Sphere scenes only (no curves, media or Klein: F = 0).
 // =====================================================================
 
-template <bool SOLO>
+// PT (SOLO worlds: every leaf a sphere or moving sphere under no instance chain): a lambertian hit is queued
+// as a point record, HitPt{o + d * t}, hit_record's own expression on the same o, d and t, so the shade
+// needs no ray (rt_device.h HitPt)
+template <bool SOLO, bool PT>
 __global__ __launch_bounds__(kExtLdsBlock, kExtLdsWaves) void k_extend_lds(const DevScene sc, const RenderParams rp,
                                                              const PathState st, const QView in, uint32_t n,
                                                              HitBuf hit, uint32_t shard_cap,
@@ -2625,6 +2647,7 @@ __global__ __launch_bounds__(kExtLdsBlock, kExtLdsWaves) void k_extend_lds(const
                                                              unsigned long long* __restrict__ err) {
     extern __shared__ uint4 s_dyn[];
     __shared__ uint32_t s_cnt[4 * 16 + 4];
+    static_assert(SOLO || !PT, "point records: SOLO worlds only");
     const LdsTree lt(sc, false, SOLO);
     if (lt.bytes() > lds_bytes || (SOLO && !sc.bvh_solo)) {                     // the carve would leave the allocation
         if (threadIdx.x == 0) { atomicOr(err, 1ull); raise_fault(RT_FAULT_LDS); }
@@ -2641,6 +2664,7 @@ __global__ __launch_bounds__(kExtLdsBlock, kExtLdsWaves) void k_extend_lds(const
         const uint32_t k = base + ext_lid();
         int cls = -1;
         HitRec hr{};
+        double py = 0.0, pz = 0.0;                         // PT, a lambertian hit: the point is (hr.t, py, pz)
         if (k < n) {
             const uint32_t i = qphys(qm, k);
             const RayRec R = st.ray[i];
@@ -2655,10 +2679,11 @@ __global__ __launch_bounds__(kExtLdsBlock, kExtLdsWaves) void k_extend_lds(const
             } else {
                 hr = HitRec{t, leaf, i};
                 cls = s_cls[leaf];
+                if (PT && cls == MAT_LAMBERTIAN) hit_point(o, d, t, hr.t, py, pz);
             }
         }
         const uint32_t slot = ext_append(cls, counts, shard_cap, s_cnt);
-        if (cls >= 0 && slot != kNoSlot) hit.h[(size_t)cls * hit.stride + slot] = hr;
+        put_hit<PT>(hit, cls, slot, hr, py, pz);
     }
 }
 
@@ -2670,7 +2695,7 @@ __global__ __launch_bounds__(kExtLdsBlock, kExtLdsWaves) void k_extend_lds(const
 // time-0 tree (no moving spheres: it serves every time).  Only rays that hit
 // something store their depth-0 state for the shade kernels.
 // =====================================================================
-template <bool ALL, bool SOLO>
+template <bool ALL, bool SOLO, bool PT>
 __global__ __launch_bounds__(kExtLdsBlock, kCameraWaves) void k_camera(const DevScene sc, const RenderParams rp,
                                                                           const PathState st, const uint32_t n,
                                                                           HitBuf hit, uint32_t shard_cap,
@@ -2679,6 +2704,7 @@ __global__ __launch_bounds__(kExtLdsBlock, kCameraWaves) void k_camera(const Dev
                                                                           unsigned long long* __restrict__ err) {
     extern __shared__ uint4 s_dyn[];
     __shared__ uint32_t s_cnt[4 * 16 + 4];
+    static_assert(SOLO || !PT, "point records: SOLO worlds only");
     const LdsTree lt(sc, ALL, SOLO);
     if (lt.bytes() > lds_bytes || (SOLO && !sc.bvh_solo)) {
         if (threadIdx.x == 0) { atomicOr(err, 2ull); raise_fault(RT_FAULT_LDS); }
@@ -2695,6 +2721,7 @@ __global__ __launch_bounds__(kExtLdsBlock, kCameraWaves) void k_camera(const Dev
         const uint32_t w = base + ext_lid();
         int cls = -1;
         HitRec hr{};
+        double py = 0.0, pz = 0.0;                         // as in k_extend_lds
         if (w < n) {
             v3 o, d;
             double time, t;
@@ -2706,15 +2733,16 @@ __global__ __launch_bounds__(kExtLdsBlock, kCameraWaves) void k_camera(const Dev
                 const v3 L = sky_radiance(sc, d);            // throughput 1: (* 1 x) = x
                 put_sample(rp, w, 1.0 * L.x, 1.0 * L.y, 1.0 * L.z);
             } else {
-                st.ray[w] = ray_rec(o, d);                          // depth-0 state for the shade kernels
-                st.tm[w] = time;
+                st.tm[w] = time;                                    // depth-0 state for the shade kernels
                 st.rng0[w] = g.ctr;
                 hr = HitRec{t, leaf, w};
                 cls = s_cls[leaf];
+                if (PT && cls == MAT_LAMBERTIAN) hit_point(o, d, t, hr.t, py, pz);   // (its shade reads no ray)
+                else st.ray[w] = ray_rec(o, d);
             }
         }
         const uint32_t slot = ext_append(cls, counts, shard_cap, s_cnt);
-        if (cls >= 0 && slot != kNoSlot) hit.h[(size_t)cls * hit.stride + slot] = hr;
+        put_hit<PT>(hit, cls, slot, hr, py, pz);
     }
 }
 
@@ -2996,12 +3024,12 @@ __device__ __forceinline__ v3 light_random(const DevLight& L, const v3 o, Rng& g
 // The hit record (material.scm's hit-record, before the material's scatter): the point on the (instance-local)
 // ray, the normal by leaf type, the record's u and v, the flip, and both taken back out of the instance
 // chain, not renormalised.  shade_hit (every shade kernel and the tail) and k_features form it here.
+// hit_record_at: the record's steps after the point — the normal at pt by leaf type, u and v, the flip; d: the
+// (local) ray's direction, which only a curve's normal reads.  The point-record shade enters here with the
+// queued point (its leaves are spheres and moving spheres under no chain).
 template <int TL>
-__device__ __forceinline__ void hit_record(const DevScene& sc, const LeafInfo& li, const v3 o0, const v3 d0,
-                                           const double time, const double t, v3& pt, v3& nrm, double& tu, double& tv) {
-    v3 o = o0, d = d0;
-    if (li.chain >= 0) chain_ray(sc.chains[li.chain], o, d);
-    pt = o + d * t;                            // point-at-parameter on the (local) ray
+__device__ __forceinline__ void hit_record_at(const DevScene& sc, const LeafInfo& li, const v3 d, const double time,
+                                              const v3 pt, v3& nrm, double& tu, double& tv) {
     if (li.type == LEAF_SPHERE) {
         nrm = (pt - mk(li.c[0], li.c[1], li.c[2])) * li.inv_r;
     } else if (li.type == LEAF_MSPHERE) {
@@ -3030,6 +3058,14 @@ __device__ __forceinline__ void hit_record(const DevScene& sc, const LeafInfo& l
         if (li.tex_kind == TK_GENERIC) hit_uv(sc, li, pt, nrm, tu, tv);
     }
     if (li.flip) nrm = nrm * -1.0;                          // flip-normals :438
+}
+template <int TL>
+__device__ __forceinline__ void hit_record(const DevScene& sc, const LeafInfo& li, const v3 o0, const v3 d0,
+                                           const double time, const double t, v3& pt, v3& nrm, double& tu, double& tv) {
+    v3 o = o0, d = d0;
+    if (li.chain >= 0) chain_ray(sc.chains[li.chain], o, d);
+    pt = o + d * t;                            // point-at-parameter on the (local) ray
+    hit_record_at<TL>(sc, li, d, time, pt, nrm, tu, tv);
     if (li.chain >= 0) chain_hit(sc.chains[li.chain], pt, nrm);
 }
 // Hit record + material (material.scm:15-111).  MATF = the material type a
@@ -3041,16 +3077,23 @@ __device__ __forceinline__ void hit_record(const DevScene& sc, const LeafInfo& l
 // light target never take it, and its constants cost scalar registers.
 // leaves: the leaf records (LDS in k_shade when the table is small, else HBM)
 // trig: rt_libm.h's sin / cos table for the lambertian bounce (an LDS copy in k_shade)
-template <int MATF, int TL = kTexPerlin, bool LS = true, bool EX = true>
+// PT (lambertian only, a point-record queue): p.o is the hit point itself and p.d and t are not read
+template <int MATF, int TL = kTexPerlin, bool LS = true, bool EX = true, bool PT = false>
 __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P, const RenderParams& rp,
                                           PathRegs& p, const double t, const int32_t leaf, v3& L,
                                           const LeafInfo* __restrict__ leaves,
                                           const double* __restrict__ trig = rtlibm::kSinCosTab) {
+    static_assert(!PT || MATF == MAT_LAMBERTIAN, "only the lambertian scatter does without the incoming ray");
     L = mk(0.0, 0.0, 0.0);
     const LeafInfo& li = leaves[leaf];                       // one record: geometry, material, texture (fields read where used)
     v3 pt, nrm;
     double tu, tv;
-    hit_record<TL>(sc, li, p.o, p.d, p.time, t, pt, nrm, tu, tv);
+    if constexpr (PT) {
+        pt = p.o;
+        hit_record_at<TL>(sc, li, p.d, p.time, pt, nrm, tu, tv);
+    } else {
+        hit_record<TL>(sc, li, p.o, p.d, p.time, t, pt, nrm, tu, tv);
+    }
     const int mt = (MATF >= 0) ? MATF : li.mtype;
     const v3 rdir = p.d;
     const bool can_continue = p.depth < (uint32_t)kMaxDepth;
@@ -3198,12 +3241,18 @@ __device__ __forceinline__ void stage_perlin(const DevScene& sc, PerlinLds& P) {
 // alone and fit 128 with no spill
 template <int MAT, int TL, bool LS, bool EX>
 constexpr int shade_waves() { return (MAT == MAT_LAMBERTIAN && EX && TL == kTexPlain && !LS) ? 4 : 1; }
-template <int MAT, int TL, bool LS, bool LL, bool EX>
-__global__ __launch_bounds__(256, (shade_waves<MAT, TL, LS, EX>())) void k_shade(const DevScene* __restrict__ scp, const RenderParams rp,
+// PT (lambertian only): hq is the queue of point records (HitPt) a SOLO LDS kernel's PT instance wrote — the
+// hit point comes from the record and no ray is gathered.  The plain-texture PT instances are held to 4 waves
+// (127-128 VGPRs, no spill; left alone the compiler takes 128-129 and another schedule: lambertian shade 179 ms
+// against 155 per C2 frame, one lane); the Perlin ones are left alone (162-170 VGPRs: at 4 waves they spill
+// 30-36 VGPRs into the noise loops, C3 -6.5 %) — profiles/point_hits/bench_vs_parent.txt
+template <int MAT, int TL, bool LS, bool LL, bool EX, bool PT = false>
+__global__ __launch_bounds__(256, ((PT && TL == kTexPlain) ? 4 : shade_waves<MAT, TL, LS, EX>())) void k_shade(const DevScene* __restrict__ scp, const RenderParams rp,
                                                                 const PathState in, const HitRec* __restrict__ hq,
                                                                 const QView qv, PathState out,
                                                                 uint32_t* __restrict__ out_counts, uint32_t shard_cap,
                                                                 const uint32_t depth) {
+    static_assert(!PT || (MAT == MAT_LAMBERTIAN && !LS && TL < kTexImage), "the point-record shades launch_shade selects");
     const DevScene& sc = *scp;                       // scene in device memory: fields load on demand
     __shared__ uint32_t s_cnt[16 + 1];
     // the lambertian bounce's sin / cos table (rt_libm.h) in LDS: its lookups are gathers
@@ -3230,10 +3279,18 @@ __global__ __launch_bounds__(256, (shade_waves<MAT, TL, LS, EX>())) void k_shade
         bool alive = false;
         PathRegs p;
         if (k < n) {
-            const HitRec H = hq[qphys(qm, k)];
-            load_path(in, H.slot, p, rp, depth);
             v3 L;
-            alive = shade_hit<MAT, TL, LS, EX>(sc, P, rp, p, H.t, H.leaf, L, leaves, kTrig ? s_trig : rtlibm::kSinCosTab);
+            if constexpr (PT) {
+                const HitPt H = reinterpret_cast<const HitPt*>(hq)[qphys(qm, k)];
+                p.o = mk(H.px, H.py, H.pz);
+                p.d = mk(0.0, 0.0, 0.0);
+                load_path<false>(in, H.slot, p, rp, depth);
+                alive = shade_hit<MAT, TL, LS, EX, true>(sc, P, rp, p, 0.0, H.leaf, L, leaves, kTrig ? s_trig : rtlibm::kSinCosTab);
+            } else {
+                const HitRec H = hq[qphys(qm, k)];
+                load_path(in, H.slot, p, rp, depth);
+                alive = shade_hit<MAT, TL, LS, EX>(sc, P, rp, p, H.t, H.leaf, L, leaves, kTrig ? s_trig : rtlibm::kSinCosTab);
+            }
             if (!alive) write_sample(rp, p, L);
         }
         const uint32_t slot = block_append<1>(alive ? 0 : -1, out_counts, shard_cap, s_cnt);
@@ -3479,15 +3536,19 @@ static ExtendKernel extend_kernel(const DevScene& sc) {
 static CurveKernel curve_kernel(const RenderParams& rp, const CurveFuse* fuse) {
     return dispatch([](auto FUSE) -> CurveKernel { return k_extend_curves<FUSE()>; }, UpTo<2>{!fuse ? 0 : rp.exact_libm ? 2 : 1});
 }
-// SOLO: the world is one BVH group
-static ExtendLdsKernel extend_lds_kernel(const DevScene& sc) {
-    return sc.bvh_solo ? k_extend_lds<true> : k_extend_lds<false>;
+// SOLO: the world is one BVH group; pt (SOLO only): lambertian hits as point records
+static ExtendLdsKernel extend_lds_kernel(const DevScene& sc, const bool pt) {
+    if (!sc.bvh_solo) return k_extend_lds<false, false>;
+    return pt ? k_extend_lds<true, true> : k_extend_lds<true, false>;
 }
 // ALL: the all-times tree (the scene has moving spheres)
-static CameraKernel camera_kernel(const DevScene& sc) {
-    return dispatch([](auto ALL, auto SOLO) -> CameraKernel { return k_camera<ALL(), SOLO()>; },
-                  !sc.tree0_any_time, sc.bvh_solo != 0);
+static CameraKernel camera_kernel(const DevScene& sc, const bool pt) {
+    return dispatch([](auto ALL, auto SOLO, auto PT) -> CameraKernel { return k_camera<ALL(), SOLO(), SOLO() && PT()>; },
+                  !sc.tree0_any_time, sc.bvh_solo != 0, pt && sc.bvh_solo);
 }
+// The scenes with point-record instances: the SOLO LDS kernels write them, and the lambertian shade reads
+// them in its instances without the light mixture and image textures (shade_kernel)
+bool point_hits_scene(const DevScene& sc) { return sc.bvh_solo && sc.light.type == LIGHT_OFF && !sc.has_image_tex; }
 // the probes' instances: plain spheres and generic trees (media forests: the stream probe only) take the
 // render's feature set, every other scene the one instance with curves, media and Klein sets
 constexpr int probe_features(const int f, const bool forest) {
@@ -3509,10 +3570,14 @@ static HitRaysLdsKernel hit_rays_lds_kernel(const DevScene& sc, const bool time0
 // LS: the light mixture, LL: the leaf records staged in LDS, EX: libm's own sin / cos for the bounce directions
 // (bounce_cos_sin: RT_OPT_EXACT_LIBM, by default in scenes with curves).  Only lambertian scatter uses the
 // light mixture and draws directions; the dielectric attenuation is constant 1, so it has no texture levels
-static ShadeKernel shade_kernel(const int mat, const DevScene& sc, const RenderParams& rp, const bool ll) {
+// pt: the lambertian queue holds point records (point_hits_scene: no light mixture, no image textures)
+static ShadeKernel shade_kernel(const int mat, const DevScene& sc, const RenderParams& rp, const bool ll, const bool pt) {
     const TexLevel tl{scene_tex_level(sc)};
     switch (mat) {
     case MAT_LAMBERTIAN:
+        if (pt)
+            return dispatch([](auto TL, auto LL, auto EX) -> ShadeKernel { return k_shade<MAT_LAMBERTIAN, TL(), false, LL(), EX(), true>; },
+                          UpTo<kTexPerlin>{tl.v}, ll, rp.exact_libm != 0);
         return dispatch([](auto TL, auto LS, auto LL, auto EX) -> ShadeKernel { return k_shade<MAT_LAMBERTIAN, TL(), LS(), LL(), EX()>; },
                       tl, sc.light.type != LIGHT_OFF, ll, rp.exact_libm != 0);
     case MAT_METAL:
@@ -3628,11 +3693,11 @@ static uint32_t lds_grid(const uint32_t n, const uint32_t max_blocks) {
     return shard_blocks(blocks > max_blocks ? max_blocks : blocks);
 }
 hipError_t launch_extend_lds(const DevScene& sc, const RenderParams& rp, const PathState& st, const QView& in,
-                             uint32_t n, const HitBuf& hit,
+                             uint32_t n, const HitBuf& hit, bool pt,
                              uint32_t shard_cap, uint32_t* counts, uint32_t max_blocks, unsigned long long* err,
                              hipStream_t s) {
     const size_t lds = extend_lds_bytes(sc);
-    hipLaunchKernelGGL(extend_lds_kernel(sc), dim3(lds_grid(n, max_blocks)), dim3(kExtLdsBlock), lds, s, sc, rp, st, in,
+    hipLaunchKernelGGL(extend_lds_kernel(sc, pt), dim3(lds_grid(n, max_blocks)), dim3(kExtLdsBlock), lds, s, sc, rp, st, in,
                        n, hit, shard_cap, counts, (uint32_t)lds, err);
     return hipGetLastError();
 }
@@ -3646,8 +3711,19 @@ static hipError_t resident_blocks(const void* f, size_t lds, uint32_t* max_block
     *max_blocks = (uint32_t)(cus * (per_cu > 0 ? per_cu : 0));
     return hipSuccess;
 }
+// (a SOLO scene's two instances, HitRec and point records, are both made ready: a render picks per launch;
+// the grid cap is the smaller residency)
+template <class Sel>
+static hipError_t resident_blocks_both(const DevScene& sc, Sel kernel, size_t lds, uint32_t* max_blocks) {
+    if (const hipError_t e = resident_blocks(reinterpret_cast<const void*>(kernel(sc, false)), lds, max_blocks)) return e;
+    if (!sc.bvh_solo) return hipSuccess;
+    uint32_t mb = 0;
+    if (const hipError_t e = resident_blocks(reinterpret_cast<const void*>(kernel(sc, true)), lds, &mb)) return e;
+    if (mb < *max_blocks) *max_blocks = mb;
+    return hipSuccess;
+}
 hipError_t extend_lds_prepare(const DevScene& sc, size_t lds, uint32_t* max_blocks) {
-    return resident_blocks(reinterpret_cast<const void*>(extend_lds_kernel(sc)), lds, max_blocks);
+    return resident_blocks_both(sc, extend_lds_kernel, lds, max_blocks);
 }
 // LDS bytes k_camera needs (0 = cannot run): the all-times tree when the scene
 // has moving spheres, else the time-0 tree
@@ -3658,12 +3734,12 @@ size_t camera_lds_bytes(const DevScene& sc) {
     return LdsTree(sc, true, sc.bvh_solo != 0).bytes();
 }
 hipError_t camera_prepare(const DevScene& sc, size_t lds, uint32_t* max_blocks) {
-    return resident_blocks(reinterpret_cast<const void*>(camera_kernel(sc)), lds, max_blocks);
+    return resident_blocks_both(sc, camera_kernel, lds, max_blocks);
 }
 hipError_t launch_camera(const DevScene& sc, const RenderParams& rp, const PathState& st, uint32_t n,
-                         const HitBuf& hit, uint32_t shard_cap, uint32_t* counts,
+                         const HitBuf& hit, bool pt, uint32_t shard_cap, uint32_t* counts,
                          size_t lds, uint32_t max_blocks, unsigned long long* err, hipStream_t s) {
-    hipLaunchKernelGGL(camera_kernel(sc), dim3(lds_grid(n, max_blocks)), dim3(kExtLdsBlock), lds, s, sc, rp, st, n, hit,
+    hipLaunchKernelGGL(camera_kernel(sc, pt), dim3(lds_grid(n, max_blocks)), dim3(kExtLdsBlock), lds, s, sc, rp, st, n, hit,
                        shard_cap, counts, (uint32_t)lds, err);
     return hipGetLastError();
 }
@@ -3679,7 +3755,7 @@ hipError_t launch_hit_rays_lds(const DevScene& sc, bool time0, size_t lds, const
 }
 constexpr size_t kShadeLeafLds = 32768;      // stage the leaf records when they fit (256 leaves)
 hipError_t launch_shade(int mat, const DevScene& sc, const DevScene* scd, const RenderParams& rp, const PathState& in,
-                        const HitBuf& hit, const QView& qv, uint32_t n_upper,
+                        const HitBuf& hit, bool pt, const QView& qv, uint32_t n_upper,
                         const PathState& out, uint32_t* out_counts, uint32_t shard_cap, uint32_t depth, hipStream_t s) {
     // grid-stride cap: each block stages the leaf records once, so fewer,
     // longer-lived blocks (2048 was best of 1024..8192 with 96M-path pools;
@@ -3690,13 +3766,14 @@ hipError_t launch_shade(int mat, const DevScene& sc, const DevScene* scd, const 
     uint32_t blocks = shard_blocks((n_upper + 255u) / 256u);
     if (blocks > max_blocks) blocks = max_blocks;
     if (blocks == 0u) blocks = kShards;
-    const HitRec* hq = hit.h + (size_t)mat * hit.stride;
+    pt = pt && mat == MAT_LAMBERTIAN;                  // the other queues hold HitRec in every launch
+    const HitRec* hq = pt ? reinterpret_cast<const HitRec*>(hit.hp) : hit.h + (size_t)mat * hit.stride;
     const size_t leaf_lds = (size_t)sc.n_leaves * sizeof(LeafInfo);
     const bool ll = leaf_lds <= kShadeLeafLds;
     // kTexPerlin / kTexImage kernels of every material carry the Perlin tables (metal albedo may be a noise texture)
     const bool pn = scene_tex_level(sc) >= kTexPerlin;
     const size_t lds = (ll ? leaf_lds : 0) + ((pn && mat != MAT_DIELECTRIC && sc.has_perlin) ? sizeof(PerlinLds) : 0);
-    hipLaunchKernelGGL(shade_kernel(mat, sc, rp, ll), dim3(blocks), dim3(256), lds, s, scd, rp, in, hq, qv, out,
+    hipLaunchKernelGGL(shade_kernel(mat, sc, rp, ll, pt), dim3(blocks), dim3(256), lds, s, scd, rp, in, hq, qv, out,
                        out_counts, shard_cap, depth);
     return hipGetLastError();
 }

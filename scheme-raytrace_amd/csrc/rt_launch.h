@@ -21,9 +21,10 @@ hipError_t launch_extend(const DevScene& sc, const DevScene* scd, const RenderPa
                          const QView& in, uint32_t n, const HitBuf& hit, uint32_t shard_cap, uint32_t* counts,
                          bool depth0, unsigned int* claim, const CurveFuse* fuse, hipStream_t s);
 // mat: the material whose hit queue (qv, at most n_upper hits) is shaded; out / out_counts: the next
-// depth's path state and its per-shard survivor counters
+// depth's path state and its per-shard survivor counters; pt: the launch that filled the queues wrote the
+// lambertian one as point records (launch_camera / launch_extend_lds with pt)
 hipError_t launch_shade(int mat, const DevScene& sc, const DevScene* scd, const RenderParams& rp, const PathState& in,
-                        const HitBuf& hit, const QView& qv, uint32_t n_upper, const PathState& out,
+                        const HitBuf& hit, bool pt, const QView& qv, uint32_t n_upper, const PathState& out,
                         uint32_t* out_counts, uint32_t shard_cap, uint32_t depth, hipStream_t s);
 // the tail kernel: finishes the n live paths of `in`; seg_count: its segment counter, followed by the
 // next-path claim; tree0_budget: LDS bytes the time-0 tree may take (0: not staged)
@@ -38,14 +39,18 @@ hipError_t extend_lds_prepare(const DevScene& sc, size_t lds, uint32_t* max_bloc
 size_t camera_lds_bytes(const DevScene& sc);
 hipError_t camera_prepare(const DevScene& sc, size_t lds, uint32_t* max_blocks);
 // raygen + the depth-0 closest hit in one kernel; lds / max_blocks: camera_lds_bytes / camera_prepare;
-// err: the word a block sets when its LDS allocation was too small
+// err: the word a block sets when its LDS allocation was too small; pt (scenes point_hits_scene accepts
+// only): lambertian hits go to hit.hp as point records and store no ray
 hipError_t launch_camera(const DevScene& sc, const RenderParams& rp, const PathState& st, uint32_t n,
-                         const HitBuf& hit, uint32_t shard_cap, uint32_t* counts, size_t lds, uint32_t max_blocks,
+                         const HitBuf& hit, bool pt, uint32_t shard_cap, uint32_t* counts, size_t lds, uint32_t max_blocks,
                          unsigned long long* err, hipStream_t s);
 // a depth >= 1 extend with the time-0 tree in LDS; max_blocks: extend_lds_prepare's; err as above
 hipError_t launch_extend_lds(const DevScene& sc, const RenderParams& rp, const PathState& st, const QView& in,
-                             uint32_t n, const HitBuf& hit, uint32_t shard_cap, uint32_t* counts,
+                             uint32_t n, const HitBuf& hit, bool pt, uint32_t shard_cap, uint32_t* counts,
                              uint32_t max_blocks, unsigned long long* err, hipStream_t s);
+// whether the scene's LDS kernels and lambertian shade have point-record instances: a SOLO world (the caller
+// checks that no leaf has an instance chain) without the light mixture or image textures
+bool point_hits_scene(const DevScene& sc);
 bool curve_persistent();                    // the host's check before a fused launch
 // rt_curve_depth_probe: bez_maxd on ray-space control points (12 doubles per curve) and 8 eps
 hipError_t launch_curve_depth(const double* cps, const double* eps8, uint32_t n, int32_t* out, hipStream_t s);

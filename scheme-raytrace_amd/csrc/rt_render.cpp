@@ -67,15 +67,23 @@ namespace {
 // profiles/r02/pool/); round 5, with the first frame on new pools excluded (a re-allocated pool's first frame
 // waits for the driver to clear the memory it reuses, tools/realloc_probe.py): 8 chunks (288Mi- or 320Mi-path
 // cap) 13 804–13 888, 10 / 12 chunks 13 657–13 711, 6 chunks (354Mi) 13 927 / 13 957 (profiles/r05/ab/pool/).
-// Default 384Mi paths, but at most what lets the render lanes' pools (~272 B per path: two path-state
-// pools, four hit queues, the sample buffer) take 65 % of the device's free memory — on a 288-GB MI355X
-// C2's frame then cuts into 6 chunks (193 GB of pools).  RT_OPT_MAX_PATHS overrides.
+// Default 384Mi paths, but at most what lets the render lanes' pools (kPoolBytesPerPath) take 65 % of the
+// device's free memory — on a 288-GB MI355X C2's frame then cuts into 6 chunks (196 GB of pools; at 288 B
+// per path it would tip into 8).  RT_OPT_MAX_PATHS overrides.
+// A lane's pools per path: state pool A (ray, path record, and the depth-0 time and draw counter: a chunk
+// starts in A, so pool B never holds depth-0 state), state pool B, the hit queues (5 x 16 B: three HitRec
+// queues and the lambertian one as HitRec or HitPt, rt_device.h HitBuf) and the sample colours — 276 B
+constexpr size_t kStateBytesB = sizeof(RayRec) + sizeof(PathRec);
+constexpr size_t kStateBytesA = kStateBytesB + sizeof(double) + sizeof(uint32_t);
+constexpr size_t kHitBytesPerPath = 3 * sizeof(HitRec) + sizeof(HitPt);
+constexpr size_t kPoolBytesPerPath = kStateBytesA + kStateBytesB + kHitBytesPerPath + 3 * sizeof(double);
+static_assert(kHitBytesPerPath == 5 * sizeof(HitRec), "HitBuf's layout: five 16-B strides");
 size_t max_paths(const Context& c, const int lanes) {
     if (c.opt_max_paths > 0) return c.opt_max_paths < 1024 ? 1024 : (size_t)c.opt_max_paths;
     size_t v = (size_t)384 << 20;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0) {
-        const size_t fit = free_b / 100 * 65 / ((size_t)std::max(1, lanes) * 272);
+        const size_t fit = free_b / 100 * 65 / ((size_t)std::max(1, lanes) * kPoolBytesPerPath);
         if (fit < v) v = fit;
     } else {
         (void)hipGetLastError();
@@ -142,20 +150,22 @@ uint32_t tail_paths(const Context& c, const uint32_t B, const int nchunks, const
     return std::max<uint32_t>(thr, B / div);
 }
 
-constexpr size_t kStateBytesPerPath = sizeof(RayRec) + sizeof(PathRec) + sizeof(double) + sizeof(uint32_t);
-
-PathState carve_state(void* base, size_t cap) {
-    PathState st;
+// depth0: pool A, which also holds raygen's time and draw counter (pool B: null, never read)
+PathState carve_state(void* base, size_t cap, const bool depth0) {
+    PathState st{};
     char* p = static_cast<char*>(base);
     st.ray = reinterpret_cast<RayRec*>(p);
     p += cap * sizeof(RayRec);
     st.path = reinterpret_cast<PathRec*>(p);
     p += cap * sizeof(PathRec);
+    if (!depth0) return st;
     st.tm = reinterpret_cast<double*>(p);
     p += cap * sizeof(double);
     st.rng0 = reinterpret_cast<uint32_t*>(p);
     return st;
 }
+// RTAMD_NO_POINT_HITS (A/B, tests; read per render): every hit queue keeps HitRec
+bool point_hits_off() { return std::getenv("RTAMD_NO_POINT_HITS") != nullptr; }
 // What every render checks first.  render_sel runs it ahead of its own checks, so the same error wins
 // however the pixels are given.
 int check_render(const Scene* s, int nx, int ny, int spp_begin, int spp_count) {
@@ -251,9 +261,9 @@ int render_impl(Scene* s, int nx, int ny, const PixSet& px, int spp_begin, int s
         if (!L.ev_cnt) HIPCHK(hipEventCreateWithFlags(&L.ev_cnt, hipEventDisableTiming));
         if (!L.ev_acc) HIPCHK(hipEventCreateWithFlags(&L.ev_acc, hipEventDisableTiming));
         if (s->profiling && !L.ev[0]) for (auto& e : L.ev) HIPCHK(hipEventCreate(&e));
-        HIPCHK(L.st_a.ensure(scap * kStateBytesPerPath));
-        HIPCHK(L.st_b.ensure(scap * kStateBytesPerPath));
-        HIPCHK(L.hit.ensure(4 * scap * sizeof(HitRec)));   // the 4 material hit queues (sharded like the survivors)
+        HIPCHK(L.st_a.ensure(scap * kStateBytesA));
+        HIPCHK(L.st_b.ensure(scap * kStateBytesB));
+        HIPCHK(L.hit.ensure(scap * kHitBytesPerPath));     // the 4 material hit queues (sharded like the survivors)
         HIPCHK(L.sb.ensure(cap * 3 * sizeof(double)));
         HIPCHK(L.counts.ensure(kIters * kCountsPerIter * sizeof(uint32_t)));
         // tail segments, next tail path / curve claim, LDS errors, the fused curve extend's continuation segments
@@ -261,8 +271,8 @@ int render_impl(Scene* s, int nx, int ny, const PixSet& px, int spp_begin, int s
         if (!L.h_counts) HIPCHK(hipHostMalloc((void**)&L.h_counts, kIters * kCountsPerIter * sizeof(uint32_t)));
         HIPCHK(hipStreamWaitEvent(L.stream, ev_in, 0));
         HIPCHK(hipMemsetAsync(L.seg_tail.p, 0, 4 * sizeof(unsigned long long), L.stream));
-        L.A = carve_state(L.st_a.p, scap);
-        L.B = carve_state(L.st_b.p, scap);
+        L.A = carve_state(L.st_a.p, scap, true);
+        L.B = carve_state(L.st_b.p, scap, false);
         L.state = Lane::IDLE;
         L.n_fin = 0;
     }
@@ -285,6 +295,8 @@ int render_impl(Scene* s, int nx, int ny, const PixSet& px, int spp_begin, int s
     // 1.4 % (profiles/r06/c2_libm/) for 26 of 15 360 horizon pixels at 256 passes, all within 1e-7
     const bool exact_libm = c->opt_exact_libm == RT_LIBM_EXACT ||
                             (c->opt_exact_libm == RT_LIBM_AUTO && (s->dev.n_bez > 0 || s->dev.has_noise_tex));
+    // point records for the lambertian queue of the launches the SOLO LDS kernels make (rt_device.h HitPt)
+    const bool point_hits = s->point_hits && !point_hits_off();
     uint64_t seq = 0;
 
     // Enqueue the lane's next step for its current path count: one wavefront
@@ -316,13 +328,17 @@ int render_impl(Scene* s, int nx, int ny, const PixSet& px, int spp_begin, int s
         }
         uint32_t* cnt = L.counts.as<uint32_t>() + L.depth * kCountsPerIter;   // [material][shard], survivors at 4
         bool fused = false;
-        HitBuf hit{L.hit.as<HitRec>(), (uint32_t)scap};
+        HitBuf hit{L.hit.as<HitRec>() + scap, (uint32_t)scap, L.hit.as<HitPt>()};
+        const bool camera = L.depth == 0 && L.fused_camera, ext_lds = L.depth > 0 && s->ext_lds;
+        // point records are what the SOLO LDS kernels write, so a render can mix the two formats across depths:
+        // one of those kernels switched off, or a chunk whose depth 0 is k_raygen + k_extend
+        const bool pt = point_hits && (camera || ext_lds);
         if (s->profiling) HIPCHK(hipEventRecord(L.ev[0], L.stream));
-        if (L.depth == 0 && L.fused_camera)     // raygen + first closest hit in one kernel
-            HIPCHK(launch_camera(s->dev, L.rp, *L.cur, L.n, hit, (uint32_t)shard_cap, cnt,
+        if (camera)                             // raygen + first closest hit in one kernel
+            HIPCHK(launch_camera(s->dev, L.rp, *L.cur, L.n, hit, pt, (uint32_t)shard_cap, cnt,
                                  s->cam_lds, s->cam_blocks, L.seg_tail.as<unsigned long long>() + 2, L.stream));
-        else if (L.depth > 0 && s->ext_lds)     // every ray of a depth >= 1 launch has time +0.0
-            HIPCHK(launch_extend_lds(s->dev, L.rp, *L.cur, L.view, L.n, hit, (uint32_t)shard_cap,
+        else if (ext_lds)                       // every ray of a depth >= 1 launch has time +0.0
+            HIPCHK(launch_extend_lds(s->dev, L.rp, *L.cur, L.view, L.n, hit, pt, (uint32_t)shard_cap,
                                      cnt, s->ext_lds_blocks, L.seg_tail.as<unsigned long long>() + 2, L.stream));
         else {
             // the curve walk's stack overflow area: one region per render lane (lanes run concurrently)
@@ -343,7 +359,7 @@ int render_impl(Scene* s, int nx, int ny, const PixSet& px, int spp_begin, int s
         for (int mt = 0; mt < 4 && !fused; ++mt) {         // (a fused launch shades its hits itself: no queues)
             if (!(s->dev.mat_mask & (1 << mt))) continue;
             const QView qv{cnt + mt * kShards * kCntStride, (uint32_t)shard_cap};
-            HIPCHK(launch_shade(mt, s->dev, s->d_dev.as<const DevScene>(), L.rp, *L.cur, hit, qv, L.n, *L.nxt, surv,
+            HIPCHK(launch_shade(mt, s->dev, s->d_dev.as<const DevScene>(), L.rp, *L.cur, hit, pt, qv, L.n, *L.nxt, surv,
                                 (uint32_t)shard_cap, (uint32_t)L.depth, L.stream));
         }
         if (s->profiling) HIPCHK(hipEventRecord(L.ev[2], L.stream));
@@ -751,6 +767,15 @@ int rt_resolve_u8_device(int ctx, const double* accum, int nx, int ny, int count
     CTX_STREAM(c, st, stream);
     HIPCHK(launch_resolve_u8(accum, (uint32_t)((size_t)nx * ny * 3), count, out, st));
     HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+/* RT_HAS_POINT_HITS */
+int rt_scene_point_hits(int scene, int* out) {
+    LOCK_SCENE(s, scene);
+    if (!s->committed) return fail("scene not committed (rt_scene_commit)");
+    if (!out) return fail("null out pointer");
+    *out = (s->point_hits && !point_hits_off()) ? 1 : 0;
     return 0;
 }
 

@@ -156,6 +156,7 @@ _SIGNATURES = {
     "rt_set_profiling": [ctypes.c_int, ctypes.c_int],
     "rt_get_scene_info": [ctypes.c_int, ctypes.POINTER(RtSceneInfo)],
     "rt_get_tree_info": [ctypes.c_int, ctypes.POINTER(RtTreeInfo)],                          # RT_HAS_GENERIC_BVH
+    "rt_scene_point_hits": [ctypes.c_int, _c_int_p],                                         # RT_HAS_POINT_HITS
     "rt_resolve_u8": [_c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_u8_p],
     "rt_shard_pixels": [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32),
                         ctypes.POINTER(ctypes.c_int64)],

@@ -220,6 +220,14 @@ def tree_info(scene_handle):
     return {name: getattr(s, name) for name, _ in s._fields_ if name != "reserved"}
 
 
+def point_hits(scene_handle):
+    """rt_scene_point_hits: whether the scene's wavefront queues lambertian hits as point records under the
+    current RTAMD_NO_POINT_HITS (images are the same either way)."""
+    o = out_int()
+    call("rt_scene_point_hits", scene_handle, ctypes.byref(o))
+    return bool(o.value)
+
+
 def render_host(scene, nx, ny, spp_begin, spp_count, seed, accum, ctx=None):
     """rt_render: accum is a host float64 array of nx*ny*3 (updated in place)."""
     h = upload(scene, ctx)
