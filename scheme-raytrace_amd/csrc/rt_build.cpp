@@ -323,9 +323,11 @@ double world_tree(const SceneDesc& s, const BuildOptions& opt, const bool generi
     d.bvh_has_bez = pre.curves() > 0 ? 1 : 0;
     COMMIT_MARK("prefix");
     // f32 box margin: 2^-21 x a radius bound R on everything a ray can start
-    // from (x4 included, see scene_radius).  The slab ends carry at most
-    // ~4 ulps x (|box| + |o|) <= 2^-22 x 1.25 R of rounding; the margin is
-    // 1.6x that.
+    // from (x4 included, see scene_radius).  With the ray's 1/d and o/d
+    // formed in f32 (rt_boxray.h, where the bound is derived) a slab end
+    // carries at most (3.5 |box - o| + 2 |o|) 2^-24 of rounding; |o| <= R and
+    // |box| <= R / 4 make that 6.4 x 2^-24 R, and the margin is 8 x 2^-24 R:
+    // 1.25x the bound (tests/csrc/box_ray_check.cpp holds it to that).
     const double margin = std::ldexp(scene_radius(s, h.f, opt.threads), -21);
     d.bvh_pad = (float)margin;
     COMMIT_MARK("radius");

@@ -37,6 +37,7 @@
 #include <hip/hip_runtime.h>
 #include "rt_device.h"
 #include "rt_launch.h"
+#include "rt_boxray.h"
 #include "rt_libm.h"
 #include "rt_wave.h"
 #include <cstdio>
@@ -1021,17 +1022,21 @@ __device__ __forceinline__ void bez_take_batch(const DevScene& sc, const BezWave
 // Per-lane BVH traversal: every lane walks its own path through the BVH2
 // (child boxes tested at the parent, nearer child first, LDS stack with a
 // block-size stride so a wave's pushes hit 64 consecutive banks).
-// f32 slab test on t = fma(box, 1/d, -o/d).  Each computed slab end is
-// within 4 ulps * (|box| + |o|) * |1/d| of the exact one; the boxes carry an
-// absolute margin above that bound for any origin inside the scene radius
-// (commit_scene), so the test only culls boxes the ray misses.
-struct BoxRay { float ix, iy, iz, px, py, pz; };     // 1/d and o/d
+// f32 slab test on t = fma(box, 1/d, -o/d), the ray's 1/d and o/d formed in f32 (rt_boxray.h: BoxRay,
+// box_ray_f32).  Each computed slab end is within (3.5 |box - o| + 2 |o|) 2^-24 |1/d| of the exact one
+// (derived there); the boxes carry an absolute margin above that bound for any origin inside the scene
+// radius (rt_build.cpp world_tree), so the test only culls boxes the ray misses.
 __device__ __forceinline__ float f32_up(const double x) {       // x >= 0 (a ray's t range)
     float f = (float)x;
     if ((double)f < x) f = __int_as_float(__float_as_int(f) + 1);
     return f;
 }
-__device__ __forceinline__ BoxRay box_ray(const v3 o, const v3 d) {
+__device__ __forceinline__ BoxRay box_ray(const v3 o, const v3 d) { return box_ray_f32(o.x, o.y, o.z, d.x, d.y, d.z); }
+// The setup in f64 (IEEE divisions, f64 clamps and products, rounded to f32 last: inside the same margin, its
+// slab ends within 2 x 2^-24 (|box| + |o|) |1/d|).  Three divisions dearer; kept for the one kernel that is
+// held to 128 VGPRs and spills 33 of them with the f32 setup against 14 with this one: the exact-libm SOLO
+// tail (k_finish).  Either setup only decides which boxes the walk enters.
+__device__ __forceinline__ BoxRay box_ray_f64(const v3 o, const v3 d) {
     const double lim = 1e30;
     const double ix = fmax(fmin(1.0 / d.x, lim), -lim);
     const double iy = fmax(fmin(1.0 / d.y, lim), -lim);
@@ -1050,7 +1055,8 @@ __device__ __forceinline__ BoxRay box_ray(const v3 o, const v3 d) {
 // depends on the origin is below 4 ulps of |o / d| per axis, so this box ray subtracts o/d - e from
 // the near plane of each axis and o/d + e from the far one, e = 2^-20 |o / d| (about 8x that bound):
 // each slab is widened by its own error, at no extra instruction in the node test (the lo and hi
-// planes take different registers instead of one).
+// planes take different registers instead of one).  This setup stays in f64 (the curve kernels were not
+// measured with an f32 one).
 struct BoxRayW { float ix, iy, iz, lx, ly, lz, hx, hy, hz; };   // 1/d; o/d adjusted for the lo / hi planes
 __device__ __forceinline__ BoxRayW box_ray_w(const v3 o, const v3 d) {
     const double lim = 1e30;
@@ -1213,7 +1219,8 @@ __device__ __forceinline__ void bvh_walk(const BR br, const double& closest, SE*
 // sphere and fsph is in leaf order, so leaf ref ~k tests fsph[k] directly
 // (no leaf record to fetch or keep in LDS).
 // SE, WIDE: bvh_walk's; 16-bit stacks take the sign-selected planes for the time-0 tree only.
-template <bool FROZEN, class SE = uint32_t, bool DIRECT = false, bool WIDE = false>
+// B64: the box ray set up in f64 (box_ray_f64).
+template <bool FROZEN, class SE = uint32_t, bool DIRECT = false, bool WIDE = false, bool B64 = false>
 __device__ __forceinline__ void bvh_closest_lane(const DevScene& sc, const v3 o, const v3 d, const double time,
                                                  double& closest, int32_t& best, SE* lstk, const int lmax,
                                                  const BvhNode2* __restrict__ nodes,
@@ -1227,6 +1234,7 @@ __device__ __forceinline__ void bvh_closest_lane(const DevScene& sc, const v3 o,
     using BR = typename std::conditional<WIDE, BoxRayW, BoxRay>::type;
     BR br;
     if constexpr (WIDE) br = box_ray_w(o, d);
+    else if constexpr (B64) br = box_ray_f64(o, d);
     else br = box_ray(o, d);
     const int32_t bs = sc.leaf_base[LEAF_SPHERE], bm = sc.leaf_base[LEAF_MSPHERE];
     int32_t fbest = -1;                                       // FROZEN: fsph index of the best hit
@@ -1842,7 +1850,8 @@ __device__ __forceinline__ int32_t closest_hit(const DevScene& sc, const v3 o0, 
 // +0.0 also walks the all-times tree, whose boxes bound every time and whose
 // moving-sphere test at time 0 computes the frozen centre with the same
 // operations — the same closest hit, so one walk is compiled instead of two.
-template <bool SOLO, bool ALL_ONLY = false>
+// B64 (SOLO): bvh_closest_lane's.
+template <bool SOLO, bool ALL_ONLY = false, bool B64 = false>
 __device__ __forceinline__ int32_t closest_hit_lds(const DevScene& sc, const v3 o, const v3 d, const double time,
                                                    double& closest, uint16_t* lstk, const int lmax, const Tree0 t0,
                                                    const TreeA ta) {
@@ -1850,11 +1859,11 @@ __device__ __forceinline__ int32_t closest_hit_lds(const DevScene& sc, const v3 
     int32_t best = -1;
     closest = kTmax;
     if (!ALL_ONLY && (sc.tree0_any_time || __double_as_longlong(time) == 0ll))
-        bvh_closest_lane<true, uint16_t, true>(sc, o, d, time, closest, best, lstk, lmax, t0.nodes, nullptr, t0.sph,
-                                               nullptr, nullptr, t0.fid);
+        bvh_closest_lane<true, uint16_t, true, false, B64>(sc, o, d, time, closest, best, lstk, lmax, t0.nodes, nullptr,
+                                                           t0.sph, nullptr, nullptr, t0.fid);
     else
-        bvh_closest_lane<false, uint16_t>(sc, o, d, time, closest, best, lstk, lmax, ta.nodes, ta.leaves, nullptr,
-                                          ta.sph, ta.msph);
+        bvh_closest_lane<false, uint16_t, false, false, B64>(sc, o, d, time, closest, best, lstk, lmax, ta.nodes,
+                                                             ta.leaves, nullptr, ta.sph, ta.msph);
     return best;
 }
 
@@ -3347,6 +3356,9 @@ __global__ __launch_bounds__(256, (finish_waves<F, TL, LSM>())) void k_finish(co
     unsigned int* next = reinterpret_cast<unsigned int*>(tail_ctl + 1);
     const QMap qm = qmap(in);
     const uint32_t lane = threadIdx.x & 63u;
+    // the exact-libm SOLO tail sits at its 128-VGPR limit with 14 VGPRs spilled, and 33 with the f32 box ray:
+    // this one instance keeps the f64 setup
+    constexpr bool kBox64 = EX && SOLO && F == 0 && TL == kTexPlain && !LSM;
     uint32_t segs = 0, pseg = 0;                    // pseg: segments of the lane's current path
     bool active = false, exhausted = false;
     PathRegs p;
@@ -3376,7 +3388,7 @@ __global__ __launch_bounds__(256, (finish_waves<F, TL, LSM>())) void k_finish(co
             if (MED) g.init(rp.k0, rp.k1, p.pix, p.smp, p.rng);
             int32_t leaf;
             if constexpr (SOLO)
-                leaf = closest_hit_lds<true>(sc, p.o, p.d, p.time, t, s_lstack16 + threadIdx.x, LS, t0, treeA_hbm(sc));
+                leaf = closest_hit_lds<true, false, kBox64>(sc, p.o, p.d, p.time, t, s_lstack16 + threadIdx.x, LS, t0, treeA_hbm(sc));
             else
                 leaf = closest_hit<F>(sc, p.o, p.d, p.time, t, s_lstack + threadIdx.x, LS,
                                       &s_bw[BEZ ? (threadIdx.x >> 6) : 0], &g, t0, treeA_hbm(sc));
