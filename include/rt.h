@@ -174,6 +174,64 @@ int rt_add_list(int scene, const int* objs, int n, int* out_obj);
  * (geometry.scm:33-50) over the flattened list, ties at one t included. */
 int rt_add_bvh(int scene, const int* objs, int n, double time0, double time1, int sah, int* out_obj);
 
+/* ---- triangles (an extension: the reference has none) --------------------
+ * Opt-in: nothing above changes.  RT_ABI_VERSION stays 7; test RT_HAS_TRIANGLES for these entry points.
+ *
+ * rt_add_triangle: the triangle v0 v1 v2 with material mat, two-sided.
+ * rt_add_mesh: nf triangles over nv vertices (verts = nv x {x, y, z}; faces = nf x 3 vertex indices; uv =
+ * nv x {u, v} texture coordinates, or NULL: the hit records' u = v = 0).  *out_obj = one list object over the
+ * triangles, in face order, so the mesh can go under rt_add_translate / rt_add_rotate_y / rt_add_flip_normals /
+ * rt_add_bvh like any object.
+ * Refused by the add call: a null pointer (uv excepted), nv < 1 or nf < 1, a vertex or a texture coordinate
+ * of a face that is not finite, a face index outside 0 .. nv - 1, a triangle whose cross(v1 - v0, v2 - v0) has
+ * zero or non-finite length (the message names the face), an invalid material, a committed scene.  The
+ * arguments are checked before the scene handle, and a refused mesh leaves the scene as it was.
+ * Refused by rt_scene_commit: a triangle in a scene with a curve, a Klein set or a constant
+ * medium; a triangle in a medium's boundary or as the light-sampling target; a triangle whose instance chain
+ * leaves it no finite world-space box.
+ *
+ * The tree.  A scene with a triangle always gets the world tree of RT_HAS_GENERIC_BVH (rt_add_bvh above),
+ * whatever RTAMD_BVH_MIN and RTAMD_BVH_GENERIC_MIN say: every triangle is a leaf of it (its box: the box of
+ * its three vertices taken out of its instance chain), and every other leaf that qualifies with them.
+ * rt_tree_info.tri_leaves counts them.  Such a scene walks device memory only (rt_hit_rays_walk refuses the
+ * LDS walks).
+ *
+ * The hit test is the watertight test of Woop, Benthin and Wald (2013): an edge shared by two triangles gets
+ * the same edge value, with opposite sign, from both, so no ray slips between them.  All arithmetic is IEEE
+ * f64 in exactly this order, no operation contracted into an FMA.  On the instance-local ray (o, d), i.e. the
+ * ray taken into the triangle's instance chain (translate: o - offset; rotate-y: (c x - s z, y, s x + c z) on
+ * o and d, outermost first), with v[k] the k-th component (0 x, 1 y, 2 z):
+ *     kz = 0;  if |d[1]| > |d[kz]| kz = 1;  if |d[2]| > |d[kz]| kz = 2
+ *     kx = (kz + 1) % 3;  ky = (kx + 1) % 3;  if d[kz] < 0 swap(kx, ky)
+ *     Sx = d[kx] / d[kz];  Sy = d[ky] / d[kz];  Sz = 1.0 / d[kz]
+ *     A = v0 - o;  B = v1 - o;  C = v2 - o                      (componentwise)
+ *     Ax = A[kx] - Sx * A[kz];  Ay = A[ky] - Sy * A[kz]          (Bx, By, Cx, Cy alike)
+ *     U = Cx * By - Cy * Bx;  V = Ax * Cy - Ay * Cx;  W = Bx * Ay - By * Ax
+ *     miss if (U < 0 || V < 0 || W < 0) && (U > 0 || V > 0 || W > 0)
+ *     det = (U + V) + W;  miss if det == 0
+ *     T = (U * (Sz * A[kz]) + V * (Sz * B[kz])) + W * (Sz * C[kz]);  t = T / det
+ *     hit iff 0.001 < t && t < closest
+ * Both sides are hit; edges and vertices are inclusive.  The comparisons are written so that a NaN passes
+ * none: a ray in the triangle's plane (det == 0, or 0/0) and a ray with a component that is not finite miss.
+ * Ties.  A triangle ties like a sphere: of the leaves of the flattened list at the smallest t the last rect
+ * wins, and if none of them is a rect, the first leaf in list order.
+ *
+ * The hit record.  With dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z and cross(a, b) = (a.y b.z - a.z b.y,
+ * a.z b.x - a.x b.z, a.x b.y - a.y b.x):
+ *   - the point is o + d * t on the instance-local ray, as for every leaf;
+ *   - the normal is the geometric one, formed once at the commit: e1 = v1 - v0, e2 = v2 - v0, n = cross(e1, e2),
+ *     normal = n * (1.0 / sqrt(dot(n, n))).  rt_add_flip_normals negates it; the instance chain takes point and
+ *     normal back out as for rects.  There are no per-vertex shading normals;
+ *   - u, v (read by image textures only): with texture coordinates (u0, v0), (u1, v1), (u2, v2) of the vertices,
+ *     w = pt - v0, b1 = dot(cross(w, e2), n) / dot(n, n), b2 = dot(cross(e1, w), n) / dot(n, n),
+ *     b0 = (1.0 - b1) - b2, u = (b0 * u0 + b1 * u1) + b2 * u2, and v alike.  Without texture coordinates
+ *     u = v = 0, as for curves.
+ * rtamd.mesh restates all of this in NumPy (hit, normal, uv). */
+#define RT_HAS_TRIANGLES 1
+int rt_add_triangle(int scene, const double v0[3], const double v1[3], const double v2[3], int mat, int* out_obj);
+int rt_add_mesh(int scene, const double* verts, int nv, const int32_t* faces, int nf, const double* uv, int mat,
+                int* out_obj);
+
 /* camera — cam:make-camera (camera.scm:63-78) evaluated on the host side;
  * the 24 doubles are the 10 slots the reference's get-ray reads. */
 int rt_make_camera(const double lookfrom[3], const double lookat[3], const double vup[3],
@@ -393,7 +451,8 @@ typedef struct rt_tree_info {
     int32_t  generic_min;     /* RTAMD_BVH_GENERIC_MIN in force at the commit */
     int32_t  segments;        /* media forests (RT_HAS_MEDIA_BVH): segments of the list, cut after each constant medium; else 0 */
     int32_t  segment_trees;   /* ... and how many of them got a tree; the counts above are then sums / maxima over those trees */
-    int32_t  reserved[4];
+    int32_t  tri_leaves;      /* triangles in the tree (RT_HAS_TRIANGLES; counted in none of the above; was reserved[0]) */
+    int32_t  reserved[3];
 } rt_tree_info;
 #define RT_HAS_GENERIC_BVH 1
 #define RT_HAS_MEDIA_BVH 1

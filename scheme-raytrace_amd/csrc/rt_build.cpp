@@ -21,6 +21,11 @@ constexpr int kLeafMax = 1;
 
 int fail_with(std::string* err, const char* msg) { *err = msg; return 1; }
 bool is_rect(const int type) { return type >= LEAF_RECT_XY && type <= LEAF_RECT_YZ; }
+// the generic tree's leaves whose records are appended in tree order (tree_records): rects and triangles
+bool is_appended(const int type) { return is_rect(type) || type == LEAF_TRI; }
+bool has_triangle(const Flattener& f) {
+    return std::any_of(f.leaves.begin(), f.leaves.end(), [](const LeafTmp& L) { return L.type == LEAF_TRI; });
+}
 // what the sphere form of the world tree takes: world-level spheres and moving spheres
 bool world_sphere(const LeafTmp& L) { return L.chain == -1 && (L.type == LEAF_SPHERE || L.type == LEAF_MSPHERE); }
 
@@ -53,11 +58,24 @@ BezierRec bezier_rec(const Obj& o, const uint32_t order) {
     b.order = order;                    // the flattened list position
     return b;
 }
-// the extend-side part of a leaf's LeafInfo, all but `local` (shade_fields adds the rest)
+TriRec tri_rec(const Obj& o) {
+    TriRec t{};
+    for (int k = 0; k < 3; ++k) { t.v0[k] = o.cp[k]; t.v1[k] = o.cp[3 + k]; t.v2[k] = o.cp[6 + k]; }
+    return t;
+}
+TriUv tri_uv(const Obj& o) {
+    TriUv q{};
+    q.has = o.has_uv ? 1 : 0;
+    for (int k = 0; k < 3; ++k) { q.u[k] = o.uv[k]; q.v[k] = o.uv[3 + k]; }
+    return q;
+}
+// the extend-side part of a leaf's LeafInfo, all but `local` (shade_fields adds the rest); a triangle's
+// normal is formed here, once (tri_normal: a degenerate one, refused by the add calls, keeps 0 0 0)
 LeafInfo leaf_info(const LeafTmp& L, const Obj& o) {
     LeafInfo li{};
     li.type = L.type; li.chain = L.chain; li.mat = o.mat; li.flip = L.flip;
     if (L.type == LEAF_SPHERE || L.type == LEAF_MSPHERE) li.inv_r = 1.0 / o.r;
+    if (L.type == LEAF_TRI) (void)tri_normal(o.cp, o.cp + 3, o.cp + 6, li.c);
     return li;
 }
 LeafGeom leaf_geom(const LeafTmp& L, const Obj& o) {
@@ -66,6 +84,7 @@ LeafGeom leaf_geom(const LeafTmp& L, const Obj& o) {
     for (int k = 0; k < 3; ++k) { g.c0[k] = o.c0[k]; g.c1[k] = o.c1[k]; }
     g.r = o.r; g.t0 = o.t0; g.t1 = o.t1;
     g.a0 = o.a0; g.a1 = o.a1; g.b0 = o.b0; g.b1 = o.b1; g.k = o.k;
+    if (L.type == LEAF_TRI) for (int k = 0; k < 9; ++k) g.v[k] = o.cp[k];
     return g;
 }
 const ChainOpRec* chain_ops(const Flattener& f, const int ch, int& n) {
@@ -98,6 +117,7 @@ double scene_radius(const SceneDesc& s, const Flattener& f, const int nt) {
             break;
         case LEAF_KLEIN: r = n3(o.c0) + 1200; break;
         case LEAF_MEDIUM: r = 0; break;
+        case LEAF_TRI: r = std::max({n3(o.cp), n3(o.cp + 3), n3(o.cp + 6)}); break;
         default:
             r = std::sqrt(3.0) * std::max({std::fabs(o.a0), std::fabs(o.a1), std::fabs(o.b0), std::fabs(o.b1),
                                            std::fabs(o.k)});
@@ -164,7 +184,7 @@ struct TreePlan {
 bool generic_ref(const SceneDesc& s, const Flattener& f, const size_t i, const double tlo, const double thi,
                  std::vector<RotEntry>& rot, PrimRef& r) {
     const LeafTmp& L = f.leaves[i];
-    if (!is_rect(L.type) && L.chain < 0) return false;
+    if (!is_appended(L.type) && L.chain < 0) return false;
     int n_ops = 0;
     const ChainOpRec* ops = chain_ops(f, L.chain, n_ops);
     r = PrimRef{};
@@ -198,7 +218,10 @@ TreePlan choose_tree_leaves(const SceneDesc& s, const Flattener& f, const std::v
     size_t n_gen = 0;
     bool plain = nseg == 1 && f.bounds.empty();
     for (const LeafTmp& L : f.leaves) plain = plain && L.type != LEAF_BEZIER && L.type != LEAF_KLEIN && L.type != LEAF_MEDIUM;
-    if (plain && f.leaves.size() >= opt.generic_min) {
+    // a scene with a triangle (plain: build_scene refused it otherwise) always gets the generic tree, whatever
+    // its size: the tree is the only place a triangle is tested, apart from list_closest
+    const bool tri = has_triangle(f);
+    if (plain && (tri || f.leaves.size() >= opt.generic_min)) {
         p.gen_ref.resize(f.leaves.size());
         p.is_gen.assign(f.leaves.size(), 0);
         for (size_t i = 0; i < f.leaves.size(); ++i) {
@@ -207,7 +230,7 @@ TreePlan choose_tree_leaves(const SceneDesc& s, const Flattener& f, const std::v
             ++n_gen;
         }
     }
-    p.generic = n_gen > 0 && n_gen >= opt.generic_min && n_world + n_gen >= opt.bvh_min;
+    p.generic = n_gen > 0 && (tri || (n_gen >= opt.generic_min && n_world + n_gen >= opt.bvh_min));
     if (!p.generic) { rot.clear(); return p; }
     p.in_tree.clear();
     for (size_t i = 0; i < f.leaves.size(); ++i)
@@ -371,6 +394,7 @@ void put_record(const SceneDesc& s, const LeafTmp& L, const int pos, const int l
     case LEAF_MSPHERE: h.msph[k] = msphere_rec(o); ll.msph[k] = li; break;
     case LEAF_BEZIER: h.bez[k] = bezier_rec(o, (uint32_t)std::max(pos, 0)); ll.bez[k] = li; break;   // (boundaries hold no curves)
     case LEAF_KLEIN: h.klein[k] = KleinRec{o.c0[0], o.c0[1], o.c0[2], 0.0}; ll.klein[k] = li; break;
+    case LEAF_TRI: h.tri[k] = tri_rec(o); h.triuv[k] = tri_uv(o); ll.tri[k] = li; break;
     default: h.rect[k] = rect_rec(o); ll.rect[k] = li;           // the three axis types share the rect array
     }
     if (pos < 0) return;
@@ -380,6 +404,7 @@ void put_record(const SceneDesc& s, const LeafTmp& L, const int pos, const int l
 // one more slot at the end of a type's arrays: its index
 int grow(HostScene& h, const int type) {
     auto one = [](auto& recs, auto& infos) { recs.resize(recs.size() + 1); infos.resize(recs.size()); return (int)recs.size() - 1; };
+    if (type == LEAF_TRI) { h.triuv.resize(h.tri.size() + 1); return one(h.tri, h.ll.tri); }
     return type == LEAF_SPHERE ? one(h.sph, h.ll.sph) : type == LEAF_MSPHERE ? one(h.msph, h.ll.msph)
          : type == LEAF_BEZIER ? one(h.bez, h.ll.bez) : type == LEAF_KLEIN ? one(h.klein, h.ll.klein) : one(h.rect, h.ll.rect);
 }
@@ -396,11 +421,11 @@ Src tree_records(const SceneDesc& s, const Prefix& pre, const bool generic, cons
     auto slot = [&](const size_t i) { return refs[i].type == LEAF_SPHERE ? pre.ns[i] : refs[i].type == LEAF_MSPHERE ? pre.nm[i] : pre.nb[i]; };
     parallel_for(refs.size(), threads, [&](const size_t b, const size_t e) {
         for (size_t i = b; i < e; ++i)
-            if (!is_rect(refs[i].type)) put_record(s, h.f.leaves[refs[i].leaf], refs[i].leaf, slot(i), h);
+            if (!is_appended(refs[i].type)) put_record(s, h.f.leaves[refs[i].leaf], refs[i].leaf, slot(i), h);
     });
     Src src(generic ? refs.size() : 0);
     for (size_t i = 0; i < src.size(); ++i) {
-        const bool rect = is_rect(refs[i].type);
+        const bool rect = is_appended(refs[i].type);          // (a rect or a triangle)
         src[i] = {refs[i].type, rect ? grow(h, refs[i].type) : slot(i)};
         if (rect) put_record(s, h.f.leaves[refs[i].leaf], refs[i].leaf, src[i].second, h);
     }
@@ -631,11 +656,12 @@ void forest_records(const SceneDesc& s, const BuildOptions& opt, const std::vect
 }
 
 // Leaf ids: spheres, moving spheres, then all rects (the three axis types share the rect array: leaf id =
-// rect base + local), curves, media, Klein sets; h.leaves in that order
+// rect base + local), curves, media, Klein sets, triangles; h.leaves in that order
 int assign_leaf_ids(const int threads, HostScene& h, std::string& err) {
     const LeafLists& ll = h.ll;
     if (ll.sph.size() != h.sph.size() || ll.msph.size() != h.msph.size() || ll.bez.size() != h.bez.size() ||
-        ll.klein.size() != h.klein.size() || ll.rect.size() != h.rect.size())
+        ll.klein.size() != h.klein.size() || ll.rect.size() != h.rect.size() || ll.tri.size() != h.tri.size() ||
+        h.triuv.size() != h.tri.size())
         return fail_with(&err, "internal: leaf records and leaf infos out of step");
     int32_t* base = h.d.leaf_base;
     base[LEAF_SPHERE] = 0;
@@ -644,7 +670,9 @@ int assign_leaf_ids(const int threads, HostScene& h, std::string& err) {
     base[LEAF_BEZIER] = base[LEAF_RECT_XY] + (int32_t)ll.rect.size();
     base[LEAF_MEDIUM] = base[LEAF_BEZIER] + (int32_t)ll.bez.size();
     base[LEAF_KLEIN] = base[LEAF_MEDIUM] + (int32_t)ll.med.size();
-    h.leaves.resize((size_t)base[LEAF_KLEIN] + ll.klein.size());
+    const int32_t tri_base = base[LEAF_KLEIN] + (int32_t)ll.klein.size();
+    base[LEAF_TRI] = ll.tri.empty() ? 0 : tri_base;          // (a scene without triangles keeps the word 0, as memset left it)
+    h.leaves.resize((size_t)tri_base + ll.tri.size());
     auto put = [&](const LeafInfo* src, const size_t n, const int32_t at) {
         parallel_for(n, threads, [&](const size_t b, const size_t e) { std::copy(src + b, src + e, h.leaves.data() + at + b); });
     };
@@ -654,6 +682,7 @@ int assign_leaf_ids(const int threads, HostScene& h, std::string& err) {
     put(ll.bez.data(), ll.bez.size(), base[LEAF_BEZIER]);
     put(ll.med.data(), ll.med.size(), base[LEAF_MEDIUM]);
     put(ll.klein.data(), ll.klein.size(), base[LEAF_KLEIN]);
+    put(ll.tri.data(), ll.tri.size(), tri_base);
     return 0;
 }
 
@@ -731,13 +760,14 @@ void tree_info(const BuildOptions& opt, const bool use_tree, const bool generic,
     if (use_tree) {
         for (const PrimRef& r : h.refs) {
             if (r.type == LEAF_BEZIER) ++ti.curve_leaves;
+            else if (r.type == LEAF_TRI) ++ti.tri_leaves;
             else if (world_sphere(h.f.leaves[(size_t)r.leaf])) ++ti.sphere_leaves;
             else ++ti.generic_leaves;
         }
         ti.nodes = (int32_t)h.bvh2.size();
         ti.nodes0 = (int32_t)(generic ? h.g0bvh2.size() : h.fbvh2.size());
     }
-    ti.group_leaves = (int32_t)h.leaves.size() - ti.sphere_leaves - ti.curve_leaves - ti.generic_leaves;
+    ti.group_leaves = (int32_t)h.leaves.size() - ti.sphere_leaves - ti.curve_leaves - ti.generic_leaves - ti.tri_leaves;
     ti.rot_entries = (int32_t)h.rot.size();
     ti.generic_min = (int32_t)opt.generic_min;
 }
@@ -747,6 +777,7 @@ void scene_fields(const SceneDesc& s, const BuildOptions& opt, const bool tree0_
     DevScene& d = h.d;
     d.n_sph = (int)h.sph.size(); d.n_msph = (int)h.msph.size(); d.n_rect = (int)h.rect.size();
     d.n_bez = (int)h.bez.size(); d.n_klein = (int)h.klein.size(); d.n_med = (int)h.med.size();
+    d.n_tri = (int)h.tri.size();
     d.n_groups = (int)h.groups.size(); d.n_bgroups = (int)h.bgroups.size();
     d.n_chains = (int)h.chains.size(); d.n_leaves = (int)h.leaves.size();
     d.n_bvh2 = (int)h.bvh2.size(); d.n_bleaf = (int)h.bleaf.size();
@@ -804,6 +835,10 @@ int Flattener::walk(int id, int flip) {
     case O_SPHERE: leaves.push_back({LEAF_SPHERE, chain_id(), flip, id}); break;
     case O_MSPHERE: leaves.push_back({LEAF_MSPHERE, chain_id(), flip, id}); break;
     case O_RECT: leaves.push_back({LEAF_RECT_XY + o.axis, chain_id(), flip, id}); break;
+    case O_TRI:
+        if (in_boundary) return fail_with(err, "a triangle cannot be (part of) a constant medium's boundary");
+        leaves.push_back({LEAF_TRI, chain_id(), flip, id});
+        break;
     case O_BEZIER: case O_KLEIN:
         if (in_boundary) return fail_with(err, "a constant medium's boundary may hold spheres, rects, boxes and instances only");
         leaves.push_back({o.type == O_BEZIER ? LEAF_BEZIER : LEAF_KLEIN, chain_id(), flip, id});
@@ -870,6 +905,17 @@ int build_scene(const SceneDesc& s, const int world, const BuildOptions& opt, Ho
     f.err = &err;
     f.leaves.reserve(s.objs.size());                 // (a hint: an object listed twice is two leaves)
     if (int rc = f.walk(world, 0)) return rc;
+    const bool tri = has_triangle(f);
+    if (tri) {                                       // (include/rt.h, "triangles": what a triangle scene may hold)
+        for (const LeafTmp& L : f.leaves)
+            if (L.type == LEAF_BEZIER || L.type == LEAF_KLEIN || L.type == LEAF_MEDIUM)
+                return fail_with(&err, "rt_scene_commit: a scene with triangles cannot hold a curve, a Klein set or a constant medium");
+    }
+    if (s.light >= 0) {
+        const Obj* L = &s.objs[s.light];
+        while (L->type == O_FLIP) L = &s.objs[L->child];
+        if (L->type == O_TRI) return fail_with(&err, "rt_scene_commit: a triangle cannot be the light-sampling target");
+    }
     std::vector<int> seg;
     const int nseg = cut_segments(f, seg);
     COMMIT_MARK("flatten");
@@ -877,11 +923,15 @@ int build_scene(const SceneDesc& s, const int world, const BuildOptions& opt, Ho
     h.forest = forest.on;
     const TreePlan plan = forest.on ? forest.leaves : choose_tree_leaves(s, f, seg, nseg, opt, h.rot);
     h.generic = plan.generic;
+    if (tri)                                         // every triangle is a leaf of the tree: no group tests one
+        for (size_t i = 0; i < f.leaves.size(); ++i)
+            if (f.leaves[i].type == LEAF_TRI && !plan.gen(i))
+                return fail_with(&err, "rt_scene_commit: a triangle's world-space box is not finite (its instance chain?)");
     if (!forest.on) h.refs = prim_boxes(s, f, plan, opt.threads);
     COMMIT_MARK("refs");
     h.ll.ord_type.assign(f.leaves.size(), -1);
     h.ll.ord_local.assign(f.leaves.size(), -1);
-    const bool use_tree = forest.on || (!h.refs.empty() && h.refs.size() >= opt.bvh_min);
+    const bool use_tree = forest.on || (!h.refs.empty() && (tri || h.refs.size() >= opt.bvh_min));
     bool tree0_direct = false;
     Src gsrc, fsrc;
     if (forest.on) {

@@ -67,7 +67,7 @@ struct Flattener {
 // type's array), -1 for media: what the leaf ids are derived from
 struct LeafLists {
     HostVec<LeafInfo> sph, msph, bez;              // (filled by threads after a resize: rt_bvh.h, NoInit)
-    std::vector<LeafInfo> rect, klein, med;
+    std::vector<LeafInfo> rect, klein, med, tri;
     std::vector<int32_t> ord_type, ord_local;
 };
 
@@ -79,6 +79,8 @@ struct HostScene {
     HostVec<BezierRec> bez;
     std::vector<KleinRec> klein;
     std::vector<MediumRec> med;
+    std::vector<TriRec> tri;                         // triangles, in tree order, and their texture coordinates
+    std::vector<TriUv> triuv;
     std::vector<Group> groups, bgroups;
     HostVec<BvhNode2> bvh2, fbvh2, g0bvh2;           // the world tree; the time-0 tree, sphere form / generic form
     HostVec<BvhLeaf> bleaf, fbleaf, g0bleaf;

@@ -189,6 +189,8 @@ int commit_scene(Scene* s, int world) {
     up(s->d_rot, h.rot, &DevScene::rot, "rot", h.generic);
     up(s->d_g0bvh2, h.g0bvh2, &DevScene::g0bvh2, "g0bvh2", gtree0);
     up(s->d_g0bleaf, h.g0bleaf, &DevScene::g0bleaf, "g0bleaf", gtree0);
+    up(s->d_tri, h.tri, &DevScene::tri, "tri", !h.tri.empty());
+    up(s->d_triuv, h.triuv, &DevScene::triuv, "triuv", !h.tri.empty());
     up(s->d_mats, s->mats, &DevScene::mats, "mats");
     up(s->d_texs, s->texs, &DevScene::texs, "texs");
     up(s->d_teximg, s->teximg, &DevScene::teximg, "teximg", d.has_image_tex != 0);

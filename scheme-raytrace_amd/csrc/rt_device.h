@@ -25,14 +25,16 @@ constexpr int kMaxChain = 4;                   // instance ops per leaf chain
 enum TexType : int32_t { TEX_CONSTANT = 0, TEX_CHECKER = 1, TEX_NOISE = 2, TEX_MARBLE = 3, TEX_IMAGE = 4 };
 enum MatType : int32_t { MAT_LAMBERTIAN = 0, MAT_METAL = 1, MAT_DIELECTRIC = 2, MAT_DIFFUSE_LIGHT = 3 };
 enum LeafType : int32_t { LEAF_SPHERE = 0, LEAF_MSPHERE = 1, LEAF_RECT_XY = 2, LEAF_RECT_XZ = 3,
-                          LEAF_RECT_YZ = 4, LEAF_BEZIER = 5, LEAF_MEDIUM = 6, LEAF_KLEIN = 7 };
-constexpr int kLeafTypes = 8;
-constexpr int32_t GROUP_BVH = 8;               // group type: BVH over world-level spheres / curves
+                          LEAF_RECT_YZ = 4, LEAF_BEZIER = 5, LEAF_MEDIUM = 6, LEAF_KLEIN = 7, LEAF_TRI = 8 };
+constexpr int kLeafTypes = 9;
+constexpr int32_t GROUP_BVH = 9;               // group type: BVH over world-level spheres / curves
 // closest-hit kernel variants: scene features compiled in (extra = constant media, Klein limit sets)
 // kFeatGeneric: the world tree holds generic leaves (rects, instanced spheres: DevScene::gleaf); such scenes
 // have no curves or Klein sets.  kFeatGeneric | kFeatExtra: a media forest, one generic tree per segment of
 // the list between constant media; the only combination the bit enters
-constexpr int kFeatCurves = 1, kFeatExtra = 2, kFeatGeneric = 4;
+// kFeatTri: the generic tree holds triangles (LEAF_TRI); compiled in exactly one set,
+// kFeatGeneric | kFeatTri (a scene with a triangle has no curve, Klein set or constant medium)
+constexpr int kFeatCurves = 1, kFeatExtra = 2, kFeatGeneric = 4, kFeatTri = 8;
 enum ChainOp : int32_t { OP_TRANSLATE = 0, OP_ROTATE_Y = 1 };
 
 struct DevTexture {            // texture.scm:12-50
@@ -52,6 +54,10 @@ struct alignas(32) MSphereRec {                                        // center
     double den, pad0, pad1, pad2;
 };
 struct alignas(64) RectRec { double a0, a1, b0, b1, k, pad0, pad1, pad2; };
+// A triangle (include/rt.h, "triangles"): its three vertices in the instance-local frame, 96 B
+struct alignas(32) TriRec { double v0[3], v1[3], v2[3], pad0, pad1, pad2; };
+// Its texture coordinates, read by hit_uv only (DevScene::triuv, one per TriRec): has = 0: none, u = v = 0
+struct alignas(8) TriUv { double u[3], v[3]; int32_t has, pad; };
 // Cubic Bezier curve of a given width (bezier.scm:61-66): control points,
 // width1 = width/2, width2 = width1^2, eps8 = 8*(width/20).
 // order: the curve's position in the flattened object list (ties between curves at one z go to the later one)
@@ -103,7 +109,8 @@ struct alignas(16) LeafInfo {
     int32_t mat, mtype, tex, tex_kind; // material id and type, its texture id and TexKind
     double mparam;                     // fuzz (metal) / ref_idx (dielectric)
     double inv_r;                      // sphere / moving sphere: (/ 1 radius) as a double
-    double c[3];                       // sphere center; moving sphere: center(0), for time-0 rays
+    double c[3];                       // sphere center; moving sphere: center(0), for time-0 rays;
+                                       // triangle: its unit geometric normal, formed at the commit
     double albedo[3];                  // TK_CONSTANT colour / TK_CHECKER_CONST even colour
     double albedo2[3];                 // TK_CHECKER_CONST odd colour
     double pad;
@@ -193,7 +200,7 @@ struct DevScene {
     const Chain* chains;   int32_t n_chains;
     const LeafInfo* leaves; int32_t n_leaves;
     const uint8_t* leaf_cls;                   // leaf id -> material type (a byte per leaf, padded to 16)
-    int32_t leaf_base[kLeafTypes];             // first leaf id of each LeafType
+    int32_t leaf_base[kLeafTypes];             // first leaf id of each LeafType (LEAF_TRI: 0 in scenes without triangles)
     const DevMaterial* mats; int32_t n_mats;
     const DevTexture* texs;  int32_t n_texs;
     const double* ranvec;                      // 256*3 (Perlin)
@@ -226,6 +233,10 @@ struct DevScene {
     const int32_t* leaf_pos;
     const BvhNode2* g0bvh2; const BvhLeaf* g0bleaf; int32_t g0bvh2_root, n_g0bvh2;
     const struct RotEntry* rot; int32_t n_rot;
+    // Triangles (kFeatTri; n_tri = 0: none): the extend-side records and, one per record, the texture
+    // coordinates the shade side's hit_uv reads.  Every triangle is a leaf of the generic tree.
+    const TriRec* tri;     int32_t n_tri;
+    const TriUv* triuv;
 };
 
 // Wavefront path state, SoA, one slot per live path (ping-pong buffers).

@@ -29,7 +29,8 @@
 // numbers / march inside the hit test; kFeatGeneric, on its own: a world tree
 // of rects and instanced spheres, bvh_closest_generic; kFeatGeneric |
 // kFeatExtra: a media forest, one such tree per segment of the list between
-// constant media), so sphere scenes run lean kernels.
+// constant media; kFeatGeneric | kFeatTri: triangles among that tree's
+// leaves), so sphere scenes run lean kernels.
 //
 // All arithmetic is f64 like the reference's flonums.  Random numbers come
 // from a Philox4x32-10 stream keyed by (seed, pixel, sample) with a per-path
@@ -1598,15 +1599,63 @@ __device__ __forceinline__ bool order_dependent(const DevScene& sc, const v3 o, 
     }
     return dep;
 }
+// Triangles (kFeatTri; include/rt.h, "triangles"): the watertight test of Woop, Benthin and Wald (2013), all
+// in f64 and in the header's operation order.  TriRay: what the test takes from the (instance-local) ray
+// alone — the axis of the direction's largest magnitude (kz; ties keep the lower axis), the two others in
+// the order that keeps the winding (kx, ky), and the shear and scale Sx, Sy, Sz — so a walk forms it once
+// for the world ray and again only for a leaf under an instance chain.
+struct TriRay { int kx, ky, kz; double Sx, Sy, Sz; };
+__device__ __forceinline__ double axis_of(const v3 a, const int k) { return k == 0 ? a.x : (k == 1 ? a.y : a.z); }
+__device__ __forceinline__ TriRay tri_ray(const v3 d) {
+    TriRay R;
+    R.kz = 0;
+    if (fabs(d.y) > fabs(axis_of(d, R.kz))) R.kz = 1;
+    if (fabs(d.z) > fabs(axis_of(d, R.kz))) R.kz = 2;
+    R.kx = R.kz == 2 ? 0 : R.kz + 1;
+    R.ky = R.kx == 2 ? 0 : R.kx + 1;
+    const double dz = axis_of(d, R.kz);
+    if (dz < 0.0) { const int k = R.kx; R.kx = R.ky; R.ky = k; }
+    R.Sx = axis_of(d, R.kx) / dz;
+    R.Sy = axis_of(d, R.ky) / dz;
+    R.Sz = 1.0 / dz;
+    return R;
+}
+// t of the ray against triangle T, or false: a miss (edges and vertices hit; a NaN passes no comparison, so a
+// ray in the triangle's plane, or one with a component that is not finite, misses)
+__device__ __forceinline__ bool tri_t(const TriRec& T, const v3 o, const TriRay& R, double& t) {
+    const v3 A = mk(T.v0[0], T.v0[1], T.v0[2]) - o, B = mk(T.v1[0], T.v1[1], T.v1[2]) - o, C = mk(T.v2[0], T.v2[1], T.v2[2]) - o;
+    const double Az = axis_of(A, R.kz), Bz = axis_of(B, R.kz), Cz = axis_of(C, R.kz);
+    const double Ax = axis_of(A, R.kx) - R.Sx * Az, Ay = axis_of(A, R.ky) - R.Sy * Az;
+    const double Bx = axis_of(B, R.kx) - R.Sx * Bz, By = axis_of(B, R.ky) - R.Sy * Bz;
+    const double Cx = axis_of(C, R.kx) - R.Sx * Cz, Cy = axis_of(C, R.ky) - R.Sy * Cz;
+    const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    if ((U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0)) return false;
+    const double det = (U + V) + W;
+    if (det == 0.0) return false;
+    const double Tn = (U * (R.Sz * Az) + V * (R.Sz * Bz)) + W * (R.Sz * Cz);
+    t = Tn / det;
+    return true;
+}
 // One leaf of the world's list against the shrinking closest: list_closest's per-leaf test (the same
 // operations on the same records, so the same t bit for bit), ties by list position.  (Two copies on purpose: with
 // one leaf_test<F, TIE> under both, k_extend_curves, through its list_closest<kFeatCurves> fall-back, ran 398 -> 383 Mrays/s.)
+// TRI (kFeatTri): the tree holds triangles; wr = the world ray's TriRay, which a triangle under no chain takes.
+template <bool TRI>
 __device__ __forceinline__ void leaf_test_generic(const DevScene& sc, const int32_t id, const v3 o0, const v3 d0,
-                                                  const double time, double& closest, int32_t& best) {
+                                                  const double time, double& closest, int32_t& best,
+                                                  const TriRay* wr = nullptr) {
     const int4 L = *reinterpret_cast<const int4*>(&sc.leaves[id]);          // type, chain, local, flip
     const int32_t type = L.x, s = L.z;
     v3 o = o0, d = d0;
     if (L.y >= 0) chain_ray(sc.chains[L.y], o, d);
+    if constexpr (TRI) {
+        if (type == LEAF_TRI) {
+            double t;
+            if (!tri_t(sc.tri[s], o, L.y >= 0 ? tri_ray(d) : *wr, t)) return;
+            if (kTmin < t && (t < closest || (t == closest && tie_take(sc, best, id, false)))) { closest = t; best = id; }
+            return;
+        }
+    }
     if (type == LEAF_SPHERE) {
         const double a = dot(d, d), ia = 1.0 / a;
         const SphereRec S = sc.sph[s];
@@ -1633,16 +1682,20 @@ __device__ __forceinline__ void leaf_test_generic(const DevScene& sc, const int3
 }
 // bvh_walk over a tree of generic leaves (nodes / leaves / root: the all-times tree or the time-0 one): each
 // leaf's gleaf range, clamped to gleaf, tested leaf by leaf.  gleaf holds spheres, moving spheres and rects
-// only, a media forest's too, so the leaf test is kFeatGeneric's whatever the scene's set.
+// only, a media forest's too, so the leaf test is kFeatGeneric's whatever the scene's set — or triangles with
+// them (TRI: kFeatGeneric | kFeatTri), whose per-ray constants for the world ray are formed once, before the walk.
+template <bool TRI>
 __device__ __forceinline__ void bvh_closest_generic(const DevScene& sc, const v3 o, const v3 d, const double time,
                                                     double& closest, int32_t& best, uint32_t* lstk, const int lmax,
                                                     const BvhNode2* __restrict__ nodes,
                                                     const BvhLeaf* __restrict__ leaves, const int32_t root) {
     WalkCount wc;                                             // (the stats build counts the sphere trees only)
+    TriRay wr{};
+    if constexpr (TRI) wr = tri_ray(d);
     bvh_walk<false>(box_ray(o, d), closest, lstk, lmax, nodes, root, wc, [&](const int32_t k) {
         const BvhLeaf L = leaves[k];
         const int gb = max(L.gb, 0), ge = min(L.gb + L.gn, sc.n_gleaf);
-        for (int g = gb; g < ge; ++g) leaf_test_generic(sc, sc.gleaf[g], o, d, time, closest, best);
+        for (int g = gb; g < ge; ++g) leaf_test_generic<TRI>(sc, sc.gleaf[g], o, d, time, closest, best, &wr);
     });
 }
 
@@ -1738,6 +1791,7 @@ __device__ __forceinline__ void list_closest(const DevScene& sc, const v3 o0, co
     constexpr bool BEZ = (F & kFeatCurves) != 0;
     constexpr bool MED = (F & kFeatExtra) != 0;
     constexpr bool FOREST = MED && (F & kFeatGeneric) != 0;
+    constexpr bool TRI = (F & kFeatTri) != 0;
     closest = kTmax;
     best = -1;
     for (int k = 0; k < sc.n_order; ++k) {
@@ -1746,6 +1800,13 @@ __device__ __forceinline__ void list_closest(const DevScene& sc, const v3 o0, co
         const int32_t type = L.x, s = L.z;
         v3 o = o0, d = d0;
         if (L.y >= 0) chain_ray(sc.chains[L.y], o, d);
+        if constexpr (TRI) {
+            if (type == LEAF_TRI) {                // in list order: like a sphere, the first leaf at the smallest t
+                double t;
+                if (tri_t(sc.tri[s], o, tri_ray(d), t) && kTmin < t && t < closest) { closest = t; best = id; }
+                continue;
+            }
+        }
         if (type == LEAF_SPHERE) {
             const double a = dot(d, d), ia = 1.0 / a;
             const SphereRec S = sc.sph[s];
@@ -1794,6 +1855,8 @@ __device__ __forceinline__ int32_t closest_hit(const DevScene& sc, const v3 o0, 
     constexpr bool BEZ = (F & kFeatCurves) != 0;
     constexpr bool GEN = (F & kFeatGeneric) != 0;
     constexpr bool FOREST = GEN && (F & kFeatExtra) != 0;    // a media forest: one generic tree per segment
+    constexpr bool TRI = (F & kFeatTri) != 0;                // triangles among the tree's leaves
+    static_assert(!TRI || F == (kFeatGeneric | kFeatTri), "triangles: the generic tree only, no media");
     int32_t best = -1;
     bool nan_t = false;
     closest = kTmax;
@@ -1811,14 +1874,14 @@ __device__ __forceinline__ int32_t closest_hit(const DevScene& sc, const v3 o0, 
         if (G.type == GROUP_BVH) {
             if constexpr (FOREST) {                             // the group carries its tree's roots
                 const bool twin = G.end != kNoTwin && __double_as_longlong(time) == 0ll;
-                bvh_closest_generic(sc, o0, d0, time, closest, best, lstk, lmax, twin ? sc.g0bvh2 : sc.bvh2,
+                bvh_closest_generic<false>(sc, o0, d0, time, closest, best, lstk, lmax, twin ? sc.g0bvh2 : sc.bvh2,
                                     twin ? sc.g0bleaf : sc.bleaf, twin ? G.end : G.begin);
                 continue;
             } else if constexpr (GEN) {
                 if (sc.g0bvh2 != nullptr && __double_as_longlong(time) == 0ll)
-                    bvh_closest_generic(sc, o0, d0, time, closest, best, lstk, lmax, sc.g0bvh2, sc.g0bleaf, sc.g0bvh2_root);
+                    bvh_closest_generic<TRI>(sc, o0, d0, time, closest, best, lstk, lmax, sc.g0bvh2, sc.g0bleaf, sc.g0bvh2_root);
                 else
-                    bvh_closest_generic(sc, o0, d0, time, closest, best, lstk, lmax, sc.bvh2, sc.bleaf, sc.bvh2_root);
+                    bvh_closest_generic<TRI>(sc, o0, d0, time, closest, best, lstk, lmax, sc.bvh2, sc.bleaf, sc.bvh2_root);
                 continue;
             }
             if (BEZ && sc.bvh_has_bez)
@@ -2884,6 +2947,7 @@ __device__ __noinline__ void sphere_uv(const v3 n, double& u, double& v) {
     u = 1.0 - (phi + kPi) / (2.0 * kPi);
     v = (theta + kPi / 2.0) / kPi;
 }
+template <bool TRI>
 __device__ __forceinline__ void hit_uv(const DevScene& sc, const LeafInfo& li, const v3 pt, const v3 n, double& u, double& v) {
     u = 0.0; v = 0.0;
     if (li.type == LEAF_SPHERE || li.type == LEAF_MSPHERE) {
@@ -2894,6 +2958,20 @@ __device__ __forceinline__ void hit_uv(const DevScene& sc, const LeafInfo& li, c
         const double b = (li.type == LEAF_RECT_XY) ? pt.y : pt.z;
         u = (a - R.a0) / (R.a1 - R.a0);
         v = (b - R.b0) / (R.b1 - R.b0);
+    } else if (TRI && li.type == LEAF_TRI) {
+        // include/rt.h, "triangles": the vertices' texture coordinates weighted by the point's barycentrics
+        const TriUv Q = sc.triuv[li.local];
+        if (Q.has) {
+            const TriRec T = sc.tri[li.local];
+            const v3 v0 = mk(T.v0[0], T.v0[1], T.v0[2]);
+            const v3 e1 = mk(T.v1[0], T.v1[1], T.v1[2]) - v0, e2 = mk(T.v2[0], T.v2[1], T.v2[2]) - v0;
+            const v3 nn = cross(e1, e2), w = pt - v0;
+            const double den = dot(nn, nn);
+            const double b1 = dot(cross(w, e2), nn) / den, b2 = dot(cross(e1, w), nn) / den;
+            const double b0 = (1.0 - b1) - b2;
+            u = (b0 * Q.u[0] + b1 * Q.u[1]) + b2 * Q.u[2];
+            v = (b0 * Q.v[0] + b1 * Q.v[1]) + b2 * Q.v[2];
+        }
     }
 }
 // t:image-texture's lookup (texture.scm:36-50 with repair R4, include/rt.h "image textures"): indices clamped
@@ -3036,7 +3114,9 @@ __device__ __forceinline__ v3 light_random(const DevLight& L, const v3 o, Rng& g
 // hit_record_at: the record's steps after the point — the normal at pt by leaf type, u and v, the flip; d: the
 // (local) ray's direction, which only a curve's normal reads.  The point-record shade enters here with the
 // queued point (its leaves are spheres and moving spheres under no chain).
-template <int TL>
+// TRI = false compiles the triangle branches out: the instances whose scenes cannot hold one (a feature set without
+// kFeatTri, the point-record shade, the fused curve shade) keep the code they had
+template <int TL, bool TRI = true>
 __device__ __forceinline__ void hit_record_at(const DevScene& sc, const LeafInfo& li, const v3 d, const double time,
                                               const v3 pt, v3& nrm, double& tu, double& tv) {
     if (li.type == LEAF_SPHERE) {
@@ -3059,22 +3139,24 @@ __device__ __forceinline__ void hit_record_at(const DevScene& sc, const LeafInfo
     } else if (li.type == LEAF_KLEIN) {
         const KleinRec K = sc.klein[li.local];
         nrm = klein_normal(mk(K.cx, K.cy, K.cz), pt);        // at ray-pos = point-at-parameter, :664
+    } else if (TRI && li.type == LEAF_TRI) {
+        nrm = mk(li.c[0], li.c[1], li.c[2]);                 // the geometric normal, formed at the commit
     } else {
         nrm = d * -1.0;                                      // curve: (v:scale (dir r) -1), bezier.scm:204
     }
     tu = 0.0; tv = 0.0;                                      // the record's u, v: read by image textures only
     if constexpr (TL >= kTexImage) {
-        if (li.tex_kind == TK_GENERIC) hit_uv(sc, li, pt, nrm, tu, tv);
+        if (li.tex_kind == TK_GENERIC) hit_uv<TRI>(sc, li, pt, nrm, tu, tv);
     }
     if (li.flip) nrm = nrm * -1.0;                          // flip-normals :438
 }
-template <int TL>
+template <int TL, bool TRI = true>
 __device__ __forceinline__ void hit_record(const DevScene& sc, const LeafInfo& li, const v3 o0, const v3 d0,
                                            const double time, const double t, v3& pt, v3& nrm, double& tu, double& tv) {
     v3 o = o0, d = d0;
     if (li.chain >= 0) chain_ray(sc.chains[li.chain], o, d);
     pt = o + d * t;                            // point-at-parameter on the (local) ray
-    hit_record_at<TL>(sc, li, d, time, pt, nrm, tu, tv);
+    hit_record_at<TL, TRI>(sc, li, d, time, pt, nrm, tu, tv);
     if (li.chain >= 0) chain_hit(sc.chains[li.chain], pt, nrm);
 }
 // Hit record + material (material.scm:15-111).  MATF = the material type a
@@ -3087,7 +3169,7 @@ __device__ __forceinline__ void hit_record(const DevScene& sc, const LeafInfo& l
 // leaves: the leaf records (LDS in k_shade when the table is small, else HBM)
 // trig: rt_libm.h's sin / cos table for the lambertian bounce (an LDS copy in k_shade)
 // PT (lambertian only, a point-record queue): p.o is the hit point itself and p.d and t are not read
-template <int MATF, int TL = kTexPerlin, bool LS = true, bool EX = true, bool PT = false>
+template <int MATF, int TL = kTexPerlin, bool LS = true, bool EX = true, bool PT = false, bool TRI = !PT>
 __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P, const RenderParams& rp,
                                           PathRegs& p, const double t, const int32_t leaf, v3& L,
                                           const LeafInfo* __restrict__ leaves,
@@ -3099,9 +3181,9 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
     double tu, tv;
     if constexpr (PT) {
         pt = p.o;
-        hit_record_at<TL>(sc, li, p.d, p.time, pt, nrm, tu, tv);
+        hit_record_at<TL, false>(sc, li, p.d, p.time, pt, nrm, tu, tv);
     } else {
-        hit_record<TL>(sc, li, p.o, p.d, p.time, t, pt, nrm, tu, tv);
+        hit_record<TL, TRI>(sc, li, p.o, p.d, p.time, t, pt, nrm, tu, tv);
     }
     const int mt = (MATF >= 0) ? MATF : li.mtype;
     const v3 rdir = p.d;
@@ -3226,7 +3308,7 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
 template <bool EX>
 __device__ __forceinline__ bool fused_shade(const DevScene& sc, const RenderParams& rp, PathRegs& p, const double t,
                                             const int32_t leaf, v3& L) {
-    return shade_hit<-1, kTexPlain, false, EX>(sc, *reinterpret_cast<const PerlinLds*>(sc.leaves), rp, p, t, leaf, L, sc.leaves);
+    return shade_hit<-1, kTexPlain, false, EX, false, false>(sc, *reinterpret_cast<const PerlinLds*>(sc.leaves), rp, p, t, leaf, L, sc.leaves);
 }
 
 template <int TL = kTexPerlin>
@@ -3396,7 +3478,7 @@ __global__ __launch_bounds__(256, (finish_waves<F, TL, LSM>())) void k_finish(co
             v3 L;
             bool cont = false;
             if (leaf < 0) L = sky_radiance(sc, p.d);
-            else cont = shade_hit<-1, TL, LSM, EX>(sc, P, rp, p, t, leaf, L, sc.leaves);
+            else cont = shade_hit<-1, TL, LSM, EX, false, (F & kFeatTri) != 0>(sc, P, rp, p, t, leaf, L, sc.leaves);
             if (!cont) { write_sample(rp, p, L); active = false; }
         }
     }
@@ -3444,7 +3526,7 @@ __global__ __launch_bounds__(256) void k_features(const DevScene sc, const Rende
             const LeafInfo& li = sc.leaves[leaf];
             v3 pt;
             double tu, tv;
-            hit_record<TL>(sc, li, o, d, time, t, pt, n, tu, tv);
+            hit_record<TL, (F & kFeatTri) != 0>(sc, li, o, d, time, t, pt, n, tu, tv);
             a = li.mtype == MAT_DIELECTRIC ? mk(1.0, 1.0, 1.0) : leaf_tex<TL>(sc, P, li, pt, tu, tv);
             tt = t;
             hit = 1.0;
@@ -3469,11 +3551,13 @@ static bool finish_generic() {               // RTAMD_FINISH_GENERIC: the group-
     const char* e = std::getenv("RTAMD_FINISH_GENERIC");  // read per launch: tests switch it inside one process
     return e != nullptr && e[0] != '0';
 }
-// A scene's closest-hit feature set: one of the six legal ones (0, kFeatCurves, kFeatExtra, both, kFeatGeneric,
-// kFeatGeneric | kFeatExtra), which dispatch below enumerates
+// A scene's closest-hit feature set: one of the seven legal ones (0, kFeatCurves, kFeatExtra, both, kFeatGeneric,
+// kFeatGeneric | kFeatExtra, kFeatGeneric | kFeatTri), which dispatch below enumerates
 struct FeatSet { int f; };
 static FeatSet scene_features(const DevScene& sc) {
-    // (build_scene: generic leaves never with curves or Klein sets; with media only in a media forest)
+    // (build_scene: generic leaves never with curves or Klein sets; with media only in a media forest;
+    // triangles always in a generic tree and never with media)
+    if (sc.n_tri > 0) return FeatSet{kFeatGeneric | kFeatTri};
     if (sc.n_gleaf > 0) return FeatSet{sc.n_med > 0 ? kFeatGeneric | kFeatExtra : kFeatGeneric};
     return FeatSet{(sc.n_bez > 0 ? kFeatCurves : 0) | (sc.n_med > 0 || sc.n_klein > 0 ? kFeatExtra : 0)};
 }
@@ -3519,6 +3603,7 @@ static auto dispatch(Fn&& f, FeatSet v, Rest... rest) {
     case kFeatCurves | kFeatExtra: return at(std::integral_constant<int, kFeatCurves | kFeatExtra>{});
     case kFeatGeneric: return at(std::integral_constant<int, kFeatGeneric>{});
     case kFeatGeneric | kFeatExtra: return at(std::integral_constant<int, kFeatGeneric | kFeatExtra>{});
+    case kFeatGeneric | kFeatTri: return at(std::integral_constant<int, kFeatGeneric | kFeatTri>{});
     case 0: return at(std::integral_constant<int, 0>{});
     default:                                    // not a set build_scene can produce: no kernel to fall back on
         std::fprintf(stderr, "rtamd: illegal closest-hit feature set %d\n", v.f);
@@ -3564,7 +3649,8 @@ bool point_hits_scene(const DevScene& sc) { return sc.bvh_solo && sc.light.type 
 // the probes' instances: plain spheres and generic trees (media forests: the stream probe only) take the
 // render's feature set, every other scene the one instance with curves, media and Klein sets
 constexpr int probe_features(const int f, const bool forest) {
-    return (f == 0 || f == kFeatGeneric || (forest && f == (kFeatGeneric | kFeatExtra))) ? f : kFeatCurves | kFeatExtra;
+    return (f == 0 || f == kFeatGeneric || f == (kFeatGeneric | kFeatTri) || (forest && f == (kFeatGeneric | kFeatExtra)))
+               ? f : kFeatCurves | kFeatExtra;
 }
 static HitRaysKernel hit_rays_kernel(const DevScene& sc) {
     return dispatch([](auto F) -> HitRaysKernel { return k_hit_rays<probe_features(F(), false)>; }, scene_features(sc));

@@ -10,11 +10,12 @@
 namespace rtamd {
 
 // What a leaf's box depends on: a sphere (c0, r), a moving sphere (c0, c1, r, t0, t1) or an axis rect
-// (a0..a1 x b0..b1 at k; XY: k on z, XZ: k on y, YZ: k on x).
+// (a0..a1 x b0..b1 at k; XY: k on z, XZ: k on y, YZ: k on x), or a triangle (its vertices v0, v1, v2).
 struct LeafGeom {
     int type;                          // LeafType
     double c0[3], c1[3], r, t0, t1;
     double a0, a1, b0, b1, k;
+    double v[9];                       // LEAF_TRI
 };
 
 // The primitive's own box in its local frame.  A moving sphere is bounded over the times [tlo, thi] a
@@ -35,6 +36,11 @@ inline void leaf_local_box(const LeafGeom& g, const double tlo, const double thi
                 const double a = g.c0[k] + dc * f0, b = g.c0[k] + dc * f1;
                 lo[k] = std::min(a, b) - rad; hi[k] = std::max(a, b) + rad;
             }
+        }
+    } else if (g.type == LEAF_TRI) {
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = std::min(g.v[k], std::min(g.v[3 + k], g.v[6 + k]));
+            hi[k] = std::max(g.v[k], std::max(g.v[3 + k], g.v[6 + k]));
         }
     } else {
         const int ia = g.type == LEAF_RECT_YZ ? 1 : 0, ib = g.type == LEAF_RECT_XY ? 1 : 2;
@@ -88,12 +94,28 @@ inline bool leaf_world_box(const LeafGeom& g, const ChainOpRec* ops, const int n
     if (g.type == LEAF_SPHERE || g.type == LEAF_MSPHERE) {
         for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(g.c0[k]) && (g.type == LEAF_SPHERE || std::isfinite(g.c1[k]));
         fin = fin && std::isfinite(g.r) && (g.type == LEAF_SPHERE || (std::isfinite(g.t0) && std::isfinite(g.t1)));
+    } else if (g.type == LEAF_TRI) {
+        for (int k = 0; k < 9; ++k) fin = fin && std::isfinite(g.v[k]);
     } else {
         fin = std::isfinite(g.a0) && std::isfinite(g.a1) && std::isfinite(g.b0) && std::isfinite(g.b1) && std::isfinite(g.k);
     }
     if (!fin) return false;
-    leaf_local_box(g, tlo, thi, lo, hi);
-    chain_box(ops, n_ops, lo, hi);
+    if (g.type == LEAF_TRI && n_ops > 0) {
+        // a triangle is the convex hull of its vertices: the box of the three taken out of the chain (as a
+        // rect's box is that of its corners), tighter under a rotation than the image of its local box
+        for (int k = 0; k < 3; ++k) { lo[k] = INFINITY; hi[k] = -INFINITY; }
+        for (int i = 0; i < 3; ++i) {
+            double p[3] = {g.v[3 * i], g.v[3 * i + 1], g.v[3 * i + 2]};
+            chain_point(ops, n_ops, p);
+            for (int k = 0; k < 3; ++k) {
+                if (std::isnan(p[k])) return false;
+                lo[k] = std::min(lo[k], p[k]); hi[k] = std::max(hi[k], p[k]);
+            }
+        }
+    } else {
+        leaf_local_box(g, tlo, thi, lo, hi);
+        chain_box(ops, n_ops, lo, hi);
+    }
     double m = 1.0;
     for (int k = 0; k < 3; ++k) {
         if (!std::isfinite(lo[k]) || !std::isfinite(hi[k]) || !(lo[k] <= hi[k])) return false;

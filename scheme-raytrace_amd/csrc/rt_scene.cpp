@@ -275,6 +275,72 @@ int rt_add_bezier_array(int scene, const double* cps, int n, double width, int m
     }
     return 0;
 }
+// Triangles (include/rt.h, "triangles").  tri_obj: the arguments' checks, made before the handle is looked at
+// so they are refused whatever it is; `face` names the triangle in the message (-1: rt_add_triangle's own)
+static int tri_obj(const char* fn, const double* v0, const double* v1, const double* v2, const int face, Obj& o) {
+    const std::string who = face < 0 ? std::string(fn) : std::string(fn) + ": face " + std::to_string(face);
+    const double* p[3] = {v0, v1, v2};
+    for (int i = 0; i < 3; ++i)
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(p[i][k])) return fail(who + " has a vertex that is not finite");
+            o.cp[3 * i + k] = p[i][k];
+        }
+    double n[3];
+    if (!tri_normal(v0, v1, v2, n))
+        return fail(who + " is degenerate (cross(v1 - v0, v2 - v0) has zero or non-finite length)");
+    o.type = O_TRI;
+    return 0;
+}
+int rt_add_triangle(int scene, const double v0[3], const double v1[3], const double v2[3], int mat, int* out) {
+    OUT_OR_FAIL(out);
+    if (!v0 || !v1 || !v2) return fail("rt_add_triangle: null vertex");
+    Obj o;
+    if (tri_obj("rt_add_triangle", v0, v1, v2, -1, o)) return 1;
+    SCENE_OR_FAIL(s, scene);
+    if (check_mat(s, mat)) return 1;
+    o.mat = mat;
+    return push_obj(s, std::move(o), out);
+}
+int rt_add_mesh(int scene, const double* verts, int nv, const int32_t* faces, int nf, const double* uv, int mat, int* out) {
+    OUT_OR_FAIL(out);
+    if (!verts || !faces) return fail("rt_add_mesh: null vertex or face array");
+    if (nv < 1 || nf < 1) return fail("rt_add_mesh: nv and nf must be at least 1");
+    // a face's triangle: its indices checked, its vertices and texture coordinates read (tri_obj's checks)
+    auto face_obj = [&](const int f, Obj& o) {
+        const int32_t* ix = faces + 3 * (size_t)f;
+        for (int k = 0; k < 3; ++k)
+            if (ix[k] < 0 || ix[k] >= nv)
+                return fail("rt_add_mesh: face " + std::to_string(f) + " has vertex index " + std::to_string(ix[k]) +
+                            " out of range (" + std::to_string(nv) + " vertices)");
+        if (tri_obj("rt_add_mesh", verts + 3 * (size_t)ix[0], verts + 3 * (size_t)ix[1], verts + 3 * (size_t)ix[2], f, o)) return 1;
+        if (uv) {
+            o.has_uv = true;
+            for (int k = 0; k < 3; ++k) { o.uv[k] = uv[2 * (size_t)ix[k]]; o.uv[3 + k] = uv[2 * (size_t)ix[k] + 1]; }
+            for (int k = 0; k < 6; ++k)
+                if (!std::isfinite(o.uv[k])) return fail("rt_add_mesh: face " + std::to_string(f) + " has a texture coordinate that is not finite");
+        }
+        return 0;
+    };
+    // first pass: every face checked before the handle is looked at (and before the scene takes anything);
+    // second pass: the triangles built in place, so the mesh is held once
+    for (int f = 0; f < nf; ++f) {
+        Obj o;
+        if (face_obj(f, o)) return 1;
+    }
+    SCENE_OR_FAIL(s, scene);
+    if (check_mat(s, mat)) return 1;
+    Obj list; list.type = O_LIST;                       // the mesh: one list over its triangles, in face order
+    list.kids.reserve((size_t)nf);
+    s->objs.reserve(s->objs.size() + (size_t)nf + 1);
+    for (int f = 0; f < nf; ++f) {
+        Obj o;
+        (void)face_obj(f, o);
+        o.mat = mat;
+        list.kids.push_back((int)s->objs.size());
+        s->objs.push_back(std::move(o));
+    }
+    return push_obj(s, std::move(list), out);
+}
 int rt_add_klein(int scene, const double center[3], int mat, int* out) {
     SCENE_OR_FAIL(s, scene);
     OUT_OR_FAIL(out);

@@ -65,7 +65,8 @@ class RtTreeInfo(ctypes.Structure):
     """rt_tree_info (RT_HAS_GENERIC_BVH): which leaves the world tree took (media forests: the trees)."""
     _fields_ = [(n, ctypes.c_int32) for n in ("sphere_leaves", "curve_leaves", "generic_leaves", "group_leaves",
                                               "nodes", "depth", "nodes0", "depth0", "rot_entries",
-                                              "generic_min", "segments", "segment_trees")] + [("reserved", ctypes.c_int32 * 4)]
+                                              "generic_min", "segments", "segment_trees", "tri_leaves")] + \
+               [("reserved", ctypes.c_int32 * 3)]
 
 
 class RtAdaptive(ctypes.Structure):
@@ -124,6 +125,9 @@ _SIGNATURES = {
     "rt_add_bezier": [ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_double,
                       ctypes.c_int, _c_int_p],
     "rt_add_bezier_array": [ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_int_p],
+    "rt_add_triangle": [ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int, _c_int_p],   # RT_HAS_TRIANGLES
+    "rt_add_mesh": [ctypes.c_int, _c_double_p, ctypes.c_int, _c_i32_p, ctypes.c_int, _c_double_p, ctypes.c_int,
+                    _c_int_p],
     "rt_add_flip_normals": [ctypes.c_int, ctypes.c_int, _c_int_p],
     "rt_add_constant_medium": [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_int_p],
     "rt_add_klein": [ctypes.c_int, _c_double_p, ctypes.c_int, _c_int_p],

@@ -146,6 +146,21 @@ class GpuBuilder:
     def klein(self, center, mat):
         return self._out("rt_add_klein", dvec(center), mat)
 
+    def triangle(self, a, b, c, mat):
+        return self._out("rt_add_triangle", dvec(a), dvec(b), dvec(c), mat)
+
+    def mesh(self, verts, faces, uvs, mat):
+        """verts (nv, 3) float64, faces (nf, 3) int32, uvs (nv, 2) float64 or None; returns the mesh's list object."""
+        verts = np.ascontiguousarray(verts, dtype=np.float64)
+        faces = np.ascontiguousarray(faces, dtype=np.int32)
+        dp = ctypes.POINTER(ctypes.c_double)
+        uv = None
+        if uvs is not None:
+            uvs = np.ascontiguousarray(uvs, dtype=np.float64)
+            uv = uvs.ctypes.data_as(dp)
+        return self._out("rt_add_mesh", verts.ctypes.data_as(dp), int(verts.shape[0]),
+                         faces.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(faces.shape[0]), uv, mat)
+
     def constant_medium(self, boundary, density, tex):
         return self._out("rt_add_constant_medium", boundary, density, tex)
 

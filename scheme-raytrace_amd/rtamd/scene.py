@@ -167,6 +167,37 @@ def bezier_array(cps, width, material):
     return Hitable("curves", arr, float(width), material)
 
 
+def make_triangle(a, b, c, material):
+    """A two-sided triangle a b c (an extension: include/rt.h, "triangles"; restated in rtamd.mesh).  Its
+    normal is the geometric one, unit(cross(b - a, c - a))."""
+    _need(material, Material, "make-triangle material")
+    a, b, c = v.vec3(*a), v.vec3(*b), v.vec3(*c)
+    from . import mesh as _mesh
+    _mesh.check_triangles([a, b, c], [(0, 1, 2)], "make-triangle")
+    return Hitable("triangle", a, b, c, material)
+
+
+def make_mesh(vertices, faces, material, uvs=None):
+    """A triangle mesh (include/rt.h, rt_add_mesh): ``vertices`` (nv, 3), ``faces`` (nf, 3) vertex indices,
+    ``uvs`` (nv, 2) texture coordinates or None (then u = v = 0).  Behaves as the list of its triangles in
+    face order, so it goes under translate / rotate_y / flip_normals like any hitable."""
+    import numpy as np
+    from . import mesh as _mesh
+    _need(material, Material, "make-mesh material")
+    vs = np.ascontiguousarray(vertices, dtype=np.float64)
+    fs = np.ascontiguousarray(faces, dtype=np.int32)
+    if vs.ndim != 2 or vs.shape[1] != 3 or vs.shape[0] < 1:
+        raise ValueError("make-mesh: vertices must have shape (nv, 3)")
+    if fs.ndim != 2 or fs.shape[1] != 3 or fs.shape[0] < 1:
+        raise ValueError("make-mesh: faces must have shape (nf, 3)")
+    if uvs is not None:
+        uvs = np.ascontiguousarray(uvs, dtype=np.float64)
+        if uvs.shape != (vs.shape[0], 2):
+            raise ValueError("make-mesh: uvs must have shape (nv, 2)")
+    _mesh.check_triangles(vs, fs, "make-mesh")
+    return Hitable("mesh", vs, fs, uvs, material)
+
+
 def make_klein(center, material):
     """g:make-klein (geometry.scm:645-673): a Kleinian limit set (six
     inversion spheres, geometry.scm:596-605) rendered by sphere tracing with
@@ -369,6 +400,12 @@ def emit(scene, b):
             r = b.list(list(range(first, first + a[0].shape[0])))
         elif o.kind == "klein":
             r = b.klein(a[0], mat(a[1]))
+        elif o.kind in ("triangle", "mesh"):
+            if not hasattr(b, "mesh"):
+                raise NotImplementedError(
+                    "triangles are not restated in %s (only the GPU builder takes them; rtamd.mesh is their "
+                    "NumPy restatement)" % type(b).__name__)
+            r = b.triangle(a[0], a[1], a[2], mat(a[3])) if o.kind == "triangle" else b.mesh(a[0], a[1], a[2], mat(a[3]))
         elif o.kind == "medium":
             r = b.constant_medium(obj(a[0]), a[1], tex(a[2]))
         elif o.kind == "flip":

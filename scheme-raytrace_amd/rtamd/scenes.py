@@ -132,6 +132,48 @@ def cornell_box(nx, ny):
     return g.make_scene(objs, cornell_camera_for(nx, ny), g.sky_color)
 
 
+def _cornell_parts():
+    """cornell-box's materials, its six rects as (axis, a0, a1, b0, b1, k, material, flipped), and its two
+    boxes as (p1, angle, offset) with the offsets lifted by 1 in y, so that no box face lies in the floor's plane."""
+    red = g.make_lambertian(g.constant_texture(v.vec3(0.65, 0.05, 0.05)))
+    white = g.make_lambertian(g.constant_texture(v.vec3(0.73, 0.73, 0.73)))
+    green = g.make_lambertian(g.constant_texture(v.vec3(0.12, 0.45, 0.15)))
+    light = g.make_diffuse_light(g.constant_texture(v.vec3(3, 3, 3)))
+    rects = [(2, 0, 555, 0, 555, 555, green, True), (2, 0, 555, 0, 555, 0, red, False),
+             (1, 213, 343, 227, 332, 554, light, True), (1, 0, 555, 0, 555, 555, white, True),
+             (1, 0, 555, 0, 555, 0, white, False), (0, 0, 555, 0, 555, 555, white, True)]
+    boxes = [(v.vec3(165, 165, 165), -18, v.vec3(130, 1, 65)), (v.vec3(165, 330, 165), 15, v.vec3(265, 1, 295))]
+    return white, rects, boxes
+
+
+def cornell_lifted(nx, ny):
+    """cornell-box with its two boxes lifted by 1, so that no two faces of the scene are coplanar: the scene
+    cornell_mesh restates with triangles, in the reference's own shapes (which the oracle can hold)."""
+    white, rects, boxes = _cornell_parts()
+    objs = []
+    for axis, a0, a1, b0, b1, k, mat, flipped in rects:
+        r = g.Hitable("rect", axis, float(a0), float(a1), float(b0), float(b1), float(k), mat)
+        objs.append(g.flip_normals(r) if flipped else r)
+    for p1, angle, off in boxes:
+        objs.append(g.translate(g.rotate_y(g.make_box(v.vec3(0, 0, 0), p1, white), angle), off))
+    return g.make_scene(objs, cornell_camera_for(nx, ny), g.sky_color)
+
+
+def cornell_mesh(nx, ny):
+    """cornell_lifted with every rect and every box face as two triangles (rtamd.mesh.rect_quad / box: the
+    geometric normals are the rects', flips included), in the same list order."""
+    from . import mesh
+    white, rects, boxes = _cornell_parts()
+    objs = []
+    for axis, a0, a1, b0, b1, k, mat, flipped in rects:
+        vs, fs, _ = mesh.rect_quad(axis, a0, a1, b0, b1, k, flipped)
+        objs.append(g.make_mesh(vs, fs, mat))
+    for p1, angle, off in boxes:
+        vs, fs, _ = mesh.box((0, 0, 0), p1)
+        objs.append(g.translate(g.rotate_y(g.make_mesh(vs, fs, white), angle), off))
+    return g.make_scene(objs, cornell_camera_for(nx, ny), g.sky_color)
+
+
 def cornell_image_textures(floor_size=(64, 64), wall_size=(32, 32)):
     """cornell_image's two images, generated from formulas: the floor a grid of warm tiles with dark joints,
     the back wall a smooth two-way colour ramp.  Returns (floor, wall) image textures."""
@@ -432,6 +474,8 @@ SCENES = {
     "cornell_smoke": cornell_smoke,
     "cornell_mixture": cornell_mixture,
     "cornell_image": cornell_image,
+    "cornell_lifted": cornell_lifted,
+    "cornell_mesh": cornell_mesh,
     "klein": klein_scene,
     "cornell_klein": cornell_klein,
     "curves": cornell_curves,
