@@ -244,6 +244,54 @@ int rt_set_camera(int scene, const double cam[RT_CAMERA_DOUBLES]);
  * -1 = off (the reference's own cosine sampling).  The reference never wires pdf.scm, so this path
  * is checked against the oracle's restatement only. */
 int rt_set_light_sampling(int scene, int light_obj);
+/* ---- light lists (an extension of the extension: "The Rest of Your Life" gives a list of hitables a pdf) ----
+ * Opt-in: nothing above changes.  RT_ABI_VERSION stays 7; test RT_HAS_LIGHT_LIST for these entry points.
+ *
+ * rt_set_light_list: the lambertian bounces' mixture samples a list of lights instead of one.
+ * Flattening.  Each objs[k] is a rect, a sphere, a triangle, an rt_add_flip_normals of one of these, or a list
+ * of such: an rt_add_list or the object rt_add_mesh returns, nested to any depth.  They flatten in order to m
+ * lights L_0 .. L_{m-1}, 1 <= m <= RT_MAX_LIGHTS.  n == 0 turns sampling off.  A light need not be a member of
+ * the world list.  A flip does not change sampling (the densities use |cosine|).  rt_set_light_list and
+ * rt_set_light_sampling each replace the other's setting: the last call wins.
+ * Refused by the call, with a message and the scene left as it was: a box, a moving sphere, a translate, a
+ * rotate-y, an rt_add_bvh, a curve, a medium or a Klein set anywhere in the list; a bad id; m = 0 from a
+ * non-empty objs; m > RT_MAX_LIGHTS; a null objs with n > 0; n < 0; a committed scene.  (rt_scene_commit keeps
+ * refusing a triangle handed to rt_set_light_sampling.)
+ *
+ * The densities.  All arithmetic is IEEE f64 in exactly this order, no operation contracted into an FMA;
+ * next() is the path's stream; dot and cross as in the triangle section.
+ *   pdf_value(o, v):  w = 1.0 / (double)m;  s = 0.0;  for i = 0 .. m-1: s = s + w * pdf_i(o, v)
+ *   random(o):        if m > 1: r = next(); i = (int)(r * (double)m); if (i > m - 1) i = m - 1
+ *                     if m == 1: no draw, i = 0
+ *                     then random_i(o)
+ * A list of one light is that light (the book's hitable_list::random always draws; this one does not): with
+ * it rt_set_light_list(&obj, 1) on a rect or sphere commits and renders exactly as rt_set_light_sampling(obj),
+ * bit for bit.  The index clamp keeps the record read in range.
+ *   rect, sphere:  pdf_i and random_i are rt_set_light_sampling's (the sphere sampler evaluates
+ *                  random-to-sphere three times, 6 draws, with the libm mode of the render: RT_OPT_EXACT_LIBM).
+ *   triangle pdf_i(o, v):  the watertight test of the triangle section on the ray (o, v) with
+ *                  closest = 999999999999; a miss gives 0; a hit at t gives distance_squared / (cosine * area),
+ *                  distance_squared = (t * t) * dot(v, v), cosine = fabs(dot(v, nu) / sqrt(dot(v, v))),
+ *                  area = 0.5 * sqrt(dot(n, n)) with n = cross(v1 - v0, v2 - v0), nu the unit normal as the
+ *                  hit record's (n * (1.0 / sqrt(dot(n, n)))); area and nu are formed once at the commit.
+ *   triangle random_i(o):  r1 = next(); r2 = next(); su = sqrt(r1); b1 = su * (1.0 - r2); b2 = su * r2;
+ *                  pnt = v0 + (e1 * b1 + e2 * b2) componentwise, e1 = v1 - v0, e2 = v2 - v0; the result is pnt - o.
+ * The mixture is rt_set_light_sampling's: the choice draw first, 0.5 * pdf_value + 0.5 * cosine density, and
+ * !(pdf > 0) ends the path.  The light loop has the fixed trip count m: no new waiting loop, no new fault bit.
+ *
+ * rt_light_probe (a test probe, as rt_hit_rays_stream is one): for point k, on the stream of (seed, pixel k,
+ * sample 0) from its first number: out_dir = random(point), out_pdf = pdf_value(point, out_dir),
+ * out_pdf_dirs = pdf_value(point, dirs[k]) (dirs and out_pdf_dirs nullable together), out_draws = the numbers
+ * consumed.  For a single light and for a list, through the device functions the shading uses; the sphere
+ * sampler takes the libm mode the scene's renders take.  Refused before any device work: a scene without light
+ * sampling, a scene not committed, null or negative arguments.
+ * rtamd.lights restates all of this in NumPy. */
+#define RT_HAS_LIGHT_LIST 1
+#define RT_MAX_LIGHTS 4096
+int rt_set_light_list(int scene, const int* objs, int n);
+int rt_light_probe(int scene, int n, const double* points /* n x 3 */, const double* dirs /* n x 3, nullable */,
+                   uint64_t seed, double* out_dir /* n x 3 */, double* out_pdf /* n */,
+                   double* out_pdf_dirs /* n, nullable with dirs */, int32_t* out_draws /* n */);
 int rt_set_sky(int scene, int sky);
 /* Perlin tables (perlin.scm:32-36): the reference draws them from the global
  * RNG at module load; here they are data.  ranvec: 256 unit vec3, perm: 256

@@ -772,8 +772,50 @@ void tree_info(const BuildOptions& opt, const bool use_tree, const bool generic,
     ti.generic_min = (int32_t)opt.generic_min;
 }
 
+// rt_set_light_sampling's target as DevLight (a rect or a sphere, flips looked through)
+void single_light(const Obj& L, DevLight& dl) {
+    if (L.type == O_RECT) {
+        dl.type = LIGHT_RECT; dl.axis = L.axis;
+        dl.a0 = L.a0; dl.a1 = L.a1; dl.b0 = L.b0; dl.b1 = L.b1; dl.k = L.k;
+    } else {
+        dl.type = LIGHT_SPHERE;
+        dl.cx = L.c0[0]; dl.cy = L.c0[1]; dl.cz = L.c0[2]; dl.r = L.r;
+    }
+}
+// The light list's records (include/rt.h, "light lists"), from its flattened ids.  One rect or sphere is the
+// single light: d.light as rt_set_light_sampling fills it, no record.
+void light_records(const SceneDesc& s, const std::vector<int>& ids, HostScene& h) {
+    if (ids.size() == 1 && s.objs[ids[0]].type != O_TRI) { single_light(s.objs[ids[0]], h.d.light); return; }
+    h.d.light.type = LIGHT_LIST;
+    h.lights.reserve(ids.size());
+    for (const int id : ids) {
+        const Obj& o = s.objs[id];
+        DevLightRec r{};
+        if (o.type == O_RECT) {
+            r.type = LIGHT_RECT; r.axis = o.axis;
+            r.t.v0[0] = o.a0; r.t.v0[1] = o.a1; r.t.v0[2] = o.b0; r.t.v1[0] = o.b1; r.t.v1[1] = o.k;
+        } else if (o.type == O_SPHERE) {
+            r.type = LIGHT_SPHERE;
+            for (int k = 0; k < 3; ++k) r.t.v0[k] = o.c0[k];
+            r.t.v1[0] = o.r;
+        } else {
+            r.type = LIGHT_TRI;
+            h.d.lights_tri = 1;
+            r.t = tri_rec(o);
+            const double* v0 = o.cp, *v1 = o.cp + 3, *v2 = o.cp + 6;
+            const double e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
+            const double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+            r.t.pad0 = 0.5 * std::sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);    // area
+            (void)tri_normal(v0, v1, v2, r.nu);
+        }
+        h.lights.push_back(r);
+    }
+    h.d.n_lights = (int32_t)h.lights.size();
+}
+
 // the counts and scene-wide flags of DevScene, the light and the camera
-void scene_fields(const SceneDesc& s, const BuildOptions& opt, const bool tree0_direct, HostScene& h) {
+void scene_fields(const SceneDesc& s, const BuildOptions& opt, const bool tree0_direct, const std::vector<int>& lights,
+                  HostScene& h) {
     DevScene& d = h.d;
     d.n_sph = (int)h.sph.size(); d.n_msph = (int)h.msph.size(); d.n_rect = (int)h.rect.size();
     d.n_bez = (int)h.bez.size(); d.n_klein = (int)h.klein.size(); d.n_med = (int)h.med.size();
@@ -798,16 +840,12 @@ void scene_fields(const SceneDesc& s, const BuildOptions& opt, const bool tree0_
         if (t.type == TEX_IMAGE) d.has_image_tex = 1;
     }
     d.sky = s.sky;
-    if (s.light >= 0) {
+    if (!lights.empty()) {
+        light_records(s, lights, h);
+    } else if (s.light >= 0) {
         const Obj* L = &s.objs[s.light];
         while (L->type == O_FLIP) L = &s.objs[L->child];
-        if (L->type == O_RECT) {
-            d.light.type = LIGHT_RECT; d.light.axis = L->axis;
-            d.light.a0 = L->a0; d.light.a1 = L->a1; d.light.b0 = L->b0; d.light.b1 = L->b1; d.light.k = L->k;
-        } else {
-            d.light.type = LIGHT_SPHERE;
-            d.light.cx = L->c0[0]; d.light.cy = L->c0[1]; d.light.cz = L->c0[2]; d.light.r = L->r;
-        }
+        single_light(*L, d.light);
     }
     for (const auto& m : s.mats) d.mat_mask |= 1 << m.type;
     static_assert(sizeof d.cam == sizeof s.cam, "rt_make_camera's doubles are DevCamera's members, in order");
@@ -882,6 +920,51 @@ int Flattener::walk(int id, int flip) {
     return rc;
 }
 
+int flatten_lights(const SceneDesc& s, const int* objs, const int n, std::vector<int>& out, std::string& err) {
+    out.clear();
+    if (n < 0) return fail_with(&err, "rt_set_light_list: n must be >= 0");
+    if (n > 0 && !objs) return fail_with(&err, "rt_set_light_list: null object list");
+    // depth-first, in order, without recursion (a list may nest to any depth); an object listed twice is two lights
+    std::vector<std::pair<int, int>> stack;          // (object, the next kid to open)
+    for (int k = 0; k < n; ++k) {
+        stack.push_back({objs[k], 0});
+        size_t flips = 0;                            // consecutive flips looked through
+        while (!stack.empty()) {
+            const int id = stack.back().first;
+            if (id < 0 || id >= (int)s.objs.size()) {
+                err = "rt_set_light_list: invalid object id " + std::to_string(id);
+                return 1;
+            }
+            const Obj& o = s.objs[id];
+            if (o.type == O_LIST) {
+                const int kid = stack.back().second++;
+                if (kid >= (int)o.kids.size()) { stack.pop_back(); continue; }
+                if (stack.size() > s.objs.size()) return fail_with(&err, "rt_set_light_list: object graph too deep (cycle?)");
+                stack.push_back({o.kids[kid], 0});
+                continue;
+            }
+            stack.pop_back();
+            if (o.type == O_FLIP) {                              // a flip does not change sampling
+                // (a chain of flips longer than the scene has objects: a cycle in a description filled directly)
+                if (++flips > s.objs.size()) return fail_with(&err, "rt_set_light_list: object graph too deep (cycle?)");
+                stack.push_back({o.child, 0});
+                continue;
+            }
+            flips = 0;
+            if (o.type != O_RECT && o.type != O_SPHERE && o.type != O_TRI)
+                return fail_with(&err, "rt_set_light_list: a light must be a rect, a sphere or a triangle (optionally "
+                                       "flipped), or a list or mesh of such");
+            if ((int)out.size() >= RT_MAX_LIGHTS) {
+                err = "rt_set_light_list: more than RT_MAX_LIGHTS (" + std::to_string(RT_MAX_LIGHTS) + ") lights";
+                return 1;
+            }
+            out.push_back(id);
+        }
+    }
+    if (n > 0 && out.empty()) return fail_with(&err, "rt_set_light_list: the list holds no light");
+    return 0;
+}
+
 BuildOptions BuildOptions::from_env() {
     BuildOptions o;
     if (const char* e = std::getenv("RTAMD_BVH_MIN")) o.bvh_min = (size_t)std::strtoull(e, nullptr, 10);
@@ -916,6 +999,9 @@ int build_scene(const SceneDesc& s, const int world, const BuildOptions& opt, Ho
         while (L->type == O_FLIP) L = &s.objs[L->child];
         if (L->type == O_TRI) return fail_with(&err, "rt_scene_commit: a triangle cannot be the light-sampling target");
     }
+    std::vector<int> lights;                         // the light list, flattened (rt_set_light_list checked it; a
+    if (!s.lights.empty())                           // SceneDesc filled directly is checked here)
+        if (flatten_lights(s, s.lights.data(), (int)s.lights.size(), lights, err)) return 1;
     std::vector<int> seg;
     const int nseg = cut_segments(f, seg);
     COMMIT_MARK("flatten");
@@ -952,7 +1038,7 @@ int build_scene(const SceneDesc& s, const int world, const BuildOptions& opt, Ho
     if (h.d.lane_stack > kLaneStack) return fail_with(&err, "internal: BVH deeper than the traversal stack");
     if (int rc = list_order(plan.generic, fsrc, gsrc, h, err)) return rc;
     tree_info(opt, use_tree, plan.generic, h);
-    scene_fields(s, opt, tree0_direct, h);
+    scene_fields(s, opt, tree0_direct, lights, h);
     for (const Obj& o : s.objs)
         if (o.mat >= (int)s.mats.size()) return fail_with(&err, "object refers to an unknown material");
     return 0;

@@ -88,6 +88,7 @@ struct HostScene {
     std::vector<SphereRec> fsph;
     std::vector<int32_t> fid, order, gleaf, leaf_pos;
     std::vector<RotEntry> rot;
+    std::vector<DevLightRec> lights;                 // the light list's records (empty: none, or one rect / sphere in d.light)
     std::vector<Chain> chains;
     HostVec<LeafInfo> leaves;
     std::vector<uint8_t> leaf_cls;
@@ -105,6 +106,11 @@ struct HostScene {
     std::vector<BvhNode> bvh_nodes;
     LeafLists ll;
 };
+
+// A light list (include/rt.h, "light lists") flattened: the ids of its m lights (rects, spheres, triangles;
+// flips looked through, lists and meshes opened), in order.  Returns 0, or 1 with the refusal's text in err:
+// a null objs with n > 0, n < 0, a bad id, a kind that cannot be a light, m = 0, m > RT_MAX_LIGHTS.
+int flatten_lights(const SceneDesc& sd, const int* objs, int n, std::vector<int>& out, std::string& err);
 
 // The host scene of the object graph under object `world`.  Returns 0, or 1 with the failure's text in err.
 int build_scene(const SceneDesc& sd, int world, const BuildOptions& opt, HostScene& h, std::string& err);

@@ -134,11 +134,18 @@ constexpr int32_t kNoTwin = INT32_MIN;
 // Light sampling target for the pdf.scm mixture (extension f2): an axis rect
 // (axis as LeafType rect order) or a sphere.  type 0 = off.
 struct DevLight {
-    int32_t type, axis, pad0, pad1;          // type: 0 off, 1 rect, 2 sphere
+    int32_t type, axis, pad0, pad1;          // type: 0 off, 1 rect, 2 sphere, 3 the list (DevScene::lights)
     double a0, a1, b0, b1, k;                // rect
     double cx, cy, cz, r;                    // sphere
 };
-enum { LIGHT_OFF = 0, LIGHT_RECT = 1, LIGHT_SPHERE = 2 };
+// LIGHT_LIST (DevLight::type only): the mixture samples DevScene::lights (include/rt.h, "light lists");
+// LIGHT_TRI (DevLightRec::type only): a triangle of that list
+enum { LIGHT_OFF = 0, LIGHT_RECT = 1, LIGHT_SPHERE = 2, LIGHT_LIST = 3, LIGHT_TRI = 4 };
+// One light of a list, 128 B.  t holds the light's numbers: a triangle's vertices (the record the leaf test
+// reads), with t.pad0 = its area; a rect's v0 = {a0, a1, b0}, v1 = {b1, k, 0}; a sphere's v0 = centre,
+// v1 = {r, 0, 0}.  nu: a triangle's unit normal.  Area and nu are formed once at the commit.
+struct alignas(32) DevLightRec { TriRec t; double nu[3]; int32_t type, axis; };
+static_assert(sizeof(DevLightRec) == 128, "DevLightRec layout");
 
 struct DevCamera {            // camera.scm:33-78 (the 10 slots)
     double llc[3], hor[3], ver[3], origin[3], w[3], u[3], v[3];
@@ -237,6 +244,10 @@ struct DevScene {
     // coordinates the shade side's hit_uv reads.  Every triangle is a leaf of the generic tree.
     const TriRec* tri;     int32_t n_tri;
     const TriUv* triuv;
+    // The light list (light.type == LIGHT_LIST; n_lights = 0: none): the mixture's m lights in list order.
+    // A list of one rect or sphere is `light` itself, with n_lights 0.
+    const DevLightRec* lights; int32_t n_lights;
+    int32_t lights_tri;                        // 1: some light of the list is a triangle
 };
 
 // Wavefront path state, SoA, one slot per live path (ping-pong buffers).

@@ -3106,6 +3106,79 @@ __device__ __forceinline__ v3 light_random(const DevLight& L, const v3 o, Rng& g
     const double z = random_to_sphere<EX>(L.r, distance_squared, g).z;
     return (uu * x + vv * y) + w * z;
 }
+// The list forms (include/rt.h, "light lists"; rtamd.lights is the restatement they match): the mean of the
+// m lights' densities, and one light picked uniformly, then sampled.  A rect or sphere record goes through
+// the functions above as the DevLight it stands for; a triangle through the leaf test's tri_t.
+// (both forms read the same five numbers of the record, v0 and v1[0..1]: filling both halves costs no load, and
+// filling one by type made the compiler keep the DevLight in scratch)
+__device__ __forceinline__ DevLight rec_light(const DevLightRec& r) {
+    DevLight L;
+    L.type = r.type; L.axis = r.axis; L.pad0 = 0; L.pad1 = 0;
+    L.a0 = r.t.v0[0]; L.a1 = r.t.v0[1]; L.b0 = r.t.v0[2]; L.b1 = r.t.v1[0]; L.k = r.t.v1[1];
+    L.cx = r.t.v0[0]; L.cy = r.t.v0[1]; L.cz = r.t.v0[2]; L.r = r.t.v1[0];
+    return L;
+}
+__device__ __forceinline__ double tri_light_pdf(const DevLightRec& r, const v3 o, const v3 v, const TriRay& R) {
+    double t;
+    if (!tri_t(r.t, o, R, t)) return 0.0;
+    if (!(kTmin < t && t < kTmax)) return 0.0;
+    const double vv = dot(v, v);
+    const double distance_squared = (t * t) * vv;
+    const double cosine = fabs(dot(v, mk(r.nu[0], r.nu[1], r.nu[2])) / sqrt(vv));
+    return distance_squared / (cosine * r.t.pad0);           // pad0: the area
+}
+// Record i of the list for the whole wave.  recs comes out of the scene in device memory, so to the compiler it
+// is a generic pointer and a plain read of recs[i] is a per-lane flat load, 16 of them per light, although the
+// address is the same in every lane.  The records are written by the commit only: read through the constant
+// address space, a wave-uniform address goes through the scalar unit (s_load) and the record lives in SGPRs.
+__device__ __forceinline__ DevLightRec uniform_rec(const DevLightRec* __restrict__ recs, const int i) {
+    typedef const __attribute__((address_space(4))) double* cdouble_p;
+    typedef const __attribute__((address_space(4))) int32_t* cint_p;
+    const cdouble_p d = (cdouble_p)reinterpret_cast<const double*>(recs + i);
+    const cint_p w = (cint_p)reinterpret_cast<const int32_t*>(recs + i);
+    static_assert(sizeof(TriRec) == 96 && sizeof(DevLightRec) == 128, "uniform_rec reads the record as 15 doubles and 2 ints");
+    DevLightRec r;
+    for (int k = 0; k < 3; ++k) { r.t.v0[k] = d[k]; r.t.v1[k] = d[3 + k]; r.t.v2[k] = d[6 + k]; r.nu[k] = d[12 + k]; }
+    r.t.pad0 = d[9]; r.t.pad1 = 0.0; r.t.pad2 = 0.0;
+    r.type = w[30]; r.axis = w[31];
+    return r;
+}
+// every lane walks all m records, each read once for the wave (uniform_rec); has_tri (DevScene::lights_tri):
+// the list holds a triangle, else the ray's triangle constants (three divisions) are not formed
+__device__ __forceinline__ double light_pdf_value(const DevLightRec* __restrict__ recs, const int m, const bool has_tri,
+                                                  const v3 o, const v3 v) {
+    const double w = 1.0 / (double)m;
+    TriRay R{};
+    if (has_tri) R = tri_ray(v);
+    double s = 0.0;
+#pragma unroll 1
+    for (int i = 0; i < m; ++i) {
+        const DevLightRec r = uniform_rec(recs, i);
+        const double p = (r.type == LIGHT_TRI) ? tri_light_pdf(r, o, v, R) : light_pdf_value(rec_light(r), o, v);
+        s = s + w * p;
+    }
+    return s;
+}
+template <bool EX>
+__device__ __forceinline__ v3 light_random(const DevLightRec* __restrict__ recs, const int m, const v3 o, Rng& g) {
+    int i = 0;
+    if (m > 1) {
+        const double r = g.next();
+        i = (int)(r * (double)m);
+        if (i > m - 1) i = m - 1;                            // keeps this lane's record read in range
+    }
+    const DevLightRec& r = recs[i];
+    if (r.type == LIGHT_TRI) {
+        const double r1 = g.next(), r2 = g.next();
+        const double su = sqrt(r1);
+        const double b1 = su * (1.0 - r2), b2 = su * r2;
+        const v3 v0 = mk(r.t.v0[0], r.t.v0[1], r.t.v0[2]);
+        const v3 e1 = mk(r.t.v1[0], r.t.v1[1], r.t.v1[2]) - v0, e2 = mk(r.t.v2[0], r.t.v2[1], r.t.v2[2]) - v0;
+        const v3 pnt = v0 + (e1 * b1 + e2 * b2);
+        return pnt - o;
+    }
+    return light_random<EX>(rec_light(r), o, g);
+}
 
 // ------------------------------------------------------------- shading
 // The hit record (material.scm's hit-record, before the material's scatter): the point on the (instance-local)
@@ -3164,12 +3237,13 @@ __device__ __forceinline__ void hit_record(const DevScene& sc, const LeafInfo& l
 // if the path continues (p holds the scattered ray, new throughput, depth+1);
 // otherwise L is the terminal radiance (emission or 0).
 // TL: the texture level (tex_value).
-// LS = false compiles the light-sampling mixture (f2) out: scenes without a
+// LS = 0 compiles the light-sampling mixture (f2) out: scenes without a
 // light target never take it, and its constants cost scalar registers.
+// LS = 1: the mixture with the single light (sc.light); LS = 2: with the light list (sc.lights).
 // leaves: the leaf records (LDS in k_shade when the table is small, else HBM)
 // trig: rt_libm.h's sin / cos table for the lambertian bounce (an LDS copy in k_shade)
 // PT (lambertian only, a point-record queue): p.o is the hit point itself and p.d and t are not read
-template <int MATF, int TL = kTexPerlin, bool LS = true, bool EX = true, bool PT = false, bool TRI = !PT>
+template <int MATF, int TL = kTexPerlin, int LS = 1, bool EX = true, bool PT = false, bool TRI = !PT>
 __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P, const RenderParams& rp,
                                           PathRegs& p, const double t, const int32_t leaf, v3& L,
                                           const LeafInfo* __restrict__ leaves,
@@ -3205,7 +3279,8 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
         const DevLight& Lt = sc.light;
         v3 dir;
         if (g.next() < 0.5) {
-            dir = light_random<EX>(Lt, pt, g);
+            if constexpr (LS == 2) dir = light_random<EX>(sc.lights, sc.n_lights, pt, g);
+            else dir = light_random<EX>(Lt, pt, g);
         } else {
             const double r1 = g.next(), r2 = g.next();
             const double r3 = g.next(), r4 = g.next();
@@ -3220,7 +3295,9 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
         }
         double cz = dot(unit(dir), axis2);
         const double cos_val = (cz > 0.0) ? div_ia(cz, kPi, kInvPi) : 0.0;
-        const double pdf_val = 0.5 * light_pdf_value(Lt, pt, dir) + 0.5 * cos_val;
+        double pdf_val;
+        if constexpr (LS == 2) pdf_val = 0.5 * light_pdf_value(sc.lights, sc.n_lights, sc.lights_tri != 0, pt, dir) + 0.5 * cos_val;
+        else pdf_val = 0.5 * light_pdf_value(Lt, pt, dir) + 0.5 * cos_val;
         if (!(pdf_val > 0.0)) return false;                 // no 0 * inf: the path ends (L = 0)
         double cosine = dot(nrm, unit(dir));
         if (cosine < 0.0) cosine = 0.0;
@@ -3308,7 +3385,7 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
 template <bool EX>
 __device__ __forceinline__ bool fused_shade(const DevScene& sc, const RenderParams& rp, PathRegs& p, const double t,
                                             const int32_t leaf, v3& L) {
-    return shade_hit<-1, kTexPlain, false, EX, false, false>(sc, *reinterpret_cast<const PerlinLds*>(sc.leaves), rp, p, t, leaf, L, sc.leaves);
+    return shade_hit<-1, kTexPlain, 0, EX, false, false>(sc, *reinterpret_cast<const PerlinLds*>(sc.leaves), rp, p, t, leaf, L, sc.leaves);
 }
 
 template <int TL = kTexPerlin>
@@ -3330,14 +3407,14 @@ __device__ __forceinline__ void stage_perlin(const DevScene& sc, PerlinLds& P) {
 // memory-bound gathers), except the exact libm's lambertian kernels without Perlin tables or the light
 // mixture (EX) at 4 waves: with the bounce angles' in-range sin / cos (rt_cos_sin) they need 137 VGPRs left
 // alone and fit 128 with no spill
-template <int MAT, int TL, bool LS, bool EX>
+template <int MAT, int TL, int LS, bool EX>
 constexpr int shade_waves() { return (MAT == MAT_LAMBERTIAN && EX && TL == kTexPlain && !LS) ? 4 : 1; }
 // PT (lambertian only): hq is the queue of point records (HitPt) a SOLO LDS kernel's PT instance wrote — the
 // hit point comes from the record and no ray is gathered.  The plain-texture PT instances are held to 4 waves
 // (127-128 VGPRs, no spill; left alone the compiler takes 128-129 and another schedule: lambertian shade 179 ms
 // against 155 per C2 frame, one lane); the Perlin ones are left alone (162-170 VGPRs: at 4 waves they spill
 // 30-36 VGPRs into the noise loops, C3 -6.5 %) — profiles/point_hits/bench_vs_parent.txt
-template <int MAT, int TL, bool LS, bool LL, bool EX, bool PT = false>
+template <int MAT, int TL, int LS, bool LL, bool EX, bool PT = false>
 __global__ __launch_bounds__(256, ((PT && TL == kTexPlain) ? 4 : shade_waves<MAT, TL, LS, EX>())) void k_shade(const DevScene* __restrict__ scp, const RenderParams rp,
                                                                 const PathState in, const HitRec* __restrict__ hq,
                                                                 const QView qv, PathState out,
@@ -3396,9 +3473,9 @@ __global__ __launch_bounds__(256, ((PT && TL == kTexPlain) ? 4 : shade_waves<MAT
 // =====================================================================
 // plain-sphere tails without Perlin / light mixture: 128 VGPRs, 4 waves per SIMD (the compiler's choice is
 // 143: 3 waves; the other variants would spill at 128)
-template <int F, int TL, bool LSM>
+template <int F, int TL, int LSM>
 constexpr int finish_waves() { return (F == 0 && TL == kTexPlain && !LSM) ? 4 : 1; }
-template <int F, int TL, bool LSM, bool SOLO = false, bool EX = false>
+template <int F, int TL, int LSM, bool SOLO = false, bool EX = false>
 __global__ __launch_bounds__(256, (finish_waves<F, TL, LSM>())) void k_finish(const DevScene* __restrict__ scp, const RenderParams rp, const PathState st,
                                                 const QView in, uint32_t n,
                                                 unsigned long long* __restrict__ tail_ctl, int tree0_lds,
@@ -3538,6 +3615,34 @@ __global__ __launch_bounds__(256) void k_features(const DevScene sc, const Rende
     rec[0] = f0; rec[1] = f1; rec[2] = f2; rec[3] = f3; rec[4] = f4; rec[5] = f5; rec[6] = f6; rec[7] = f7;
 }
 
+// k_light_probe<LS, EX> — rt_light_probe (include/rt.h, "light lists"): the mixture's light sampler and density
+// as shade_hit calls them, point k on the stream of (seed, pixel k, sample 0) from its first number.
+// LS: 1 the single light, 2 the list; EX: the sphere sampler's libm mode.  dirs / out_pdf_dirs: null together.
+template <int LS, bool EX>
+__global__ __launch_bounds__(256) void k_light_probe(const DevScene* __restrict__ scp, const double* __restrict__ points,
+                                                     const double* __restrict__ dirs, const uint32_t n,
+                                                     const uint32_t k0, const uint32_t k1, double* __restrict__ out_dir,
+                                                     double* __restrict__ out_pdf, double* __restrict__ out_pdf_dirs,
+                                                     int32_t* __restrict__ out_draws) {
+    const DevScene& sc = *scp;
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= n) return;
+    const v3 o = mk(points[3 * (size_t)k], points[3 * (size_t)k + 1], points[3 * (size_t)k + 2]);
+    Rng g;
+    g.init(k0, k1, k, 0u, 0u);
+    const auto pdf = [&](const v3 v) {
+        if constexpr (LS == 2) return light_pdf_value(sc.lights, sc.n_lights, sc.lights_tri != 0, o, v);
+        else return light_pdf_value(sc.light, o, v);
+    };
+    v3 d;
+    if constexpr (LS == 2) d = light_random<EX>(sc.lights, sc.n_lights, o, g);
+    else d = light_random<EX>(sc.light, o, g);
+    out_dir[3 * (size_t)k] = d.x; out_dir[3 * (size_t)k + 1] = d.y; out_dir[3 * (size_t)k + 2] = d.z;
+    out_pdf[k] = pdf(d);
+    if (dirs) out_pdf_dirs[k] = pdf(mk(dirs[3 * (size_t)k], dirs[3 * (size_t)k + 1], dirs[3 * (size_t)k + 2]));
+    out_draws[k] = (int32_t)g.ctr;
+}
+
 // ------------------------------------------------------------ launchers
 // (errors pass up as `if (const hipError_t e = call) return e;`: hipSuccess is 0)
 hipError_t launch_raygen(const DevScene& sc, const RenderParams& rp, const PathState& st,
@@ -3665,7 +3770,11 @@ static HitRaysLdsKernel hit_rays_lds_kernel(const DevScene& sc, const bool time0
     return dispatch([](auto ALL, auto SOLO) -> HitRaysLdsKernel { return k_hit_rays_lds<false, ALL(), SOLO()>; },
                   !sc.tree0_any_time, sc.bvh_solo != 0);
 }
-// LS: the light mixture, LL: the leaf records staged in LDS, EX: libm's own sin / cos for the bounce directions
+// the mixture a scene's lambertian shading takes (shade_hit's LS): 0 none, 1 the single light, 2 the light list
+static UpTo<2> light_mode(const DevScene& sc) {
+    return UpTo<2>{sc.light.type == LIGHT_OFF ? 0 : sc.light.type == LIGHT_LIST ? 2 : 1};
+}
+// LS: the light mixture (light_mode), LL: the leaf records staged in LDS, EX: libm's own sin / cos for the bounce directions
 // (bounce_cos_sin: RT_OPT_EXACT_LIBM, by default in scenes with curves).  Only lambertian scatter uses the
 // light mixture and draws directions; the dielectric attenuation is constant 1, so it has no texture levels
 // pt: the lambertian queue holds point records (point_hits_scene: no light mixture, no image textures)
@@ -3677,7 +3786,7 @@ static ShadeKernel shade_kernel(const int mat, const DevScene& sc, const RenderP
             return dispatch([](auto TL, auto LL, auto EX) -> ShadeKernel { return k_shade<MAT_LAMBERTIAN, TL(), false, LL(), EX(), true>; },
                           UpTo<kTexPerlin>{tl.v}, ll, rp.exact_libm != 0);
         return dispatch([](auto TL, auto LS, auto LL, auto EX) -> ShadeKernel { return k_shade<MAT_LAMBERTIAN, TL(), LS(), LL(), EX()>; },
-                      tl, sc.light.type != LIGHT_OFF, ll, rp.exact_libm != 0);
+                      tl, light_mode(sc), ll, rp.exact_libm != 0);
     case MAT_METAL:
         return dispatch([](auto TL, auto LL) -> ShadeKernel { return k_shade<MAT_METAL, TL(), false, LL(), false>; }, tl, ll);
     case MAT_DIELECTRIC:
@@ -3698,12 +3807,12 @@ static FinishKernel finish_kernel(const DevScene& sc, const RenderParams& rp, co
     const FeatSet f = scene_features(sc);
     const int tl = finish_tex_level(sc);
     const bool ex = rp.exact_libm != 0;
-    if (f.f > 0)
-        return dispatch([](auto F, auto IMG, auto EX) -> FinishKernel {
-            return k_finish<F(), IMG() ? kTexImage : kTexPerlin, true, false, EX()>;
-        }, f, tl == kTexImage, ex);
+    if (f.f > 0)                                     // (every such instance carries the mixture: the single light's, or the list's)
+        return dispatch([](auto F, auto LIST, auto IMG, auto EX) -> FinishKernel {
+            return k_finish<F(), IMG() ? kTexImage : kTexPerlin, LIST() ? 2 : 1, false, EX()>;
+        }, f, light_mode(sc).v == 2, tl == kTexImage, ex);
     return dispatch([](auto TL, auto LS, auto SOLO, auto EX) -> FinishKernel { return k_finish<0, TL(), LS(), SOLO(), EX()>; },
-                  TexLevel{tl}, sc.light.type != LIGHT_OFF, solo, ex);
+                  TexLevel{tl}, light_mode(sc), solo, ex);
 }
 static FeaturesKernel features_kernel(const DevScene& sc) {
     return dispatch([](auto F, auto TL) -> FeaturesKernel { return k_features<F(), TL()>; },
@@ -3777,6 +3886,20 @@ hipError_t launch_features(const DevScene& sc, const RenderParams& rp, uint32_t 
     const size_t lds = lane_stack_lds(sc) +
                        ((scene_tex_level(sc) >= kTexPerlin && sc.has_perlin) ? sizeof(PerlinLds) : 0);
     hipLaunchKernelGGL(features_kernel(sc), dim3(blocks), dim3(256), lds, s, sc, rp, S, feat);
+    return hipGetLastError();
+}
+hipError_t launch_light_probe(const DevScene& sc, const DevScene* scd, bool exact_libm, const double* points,
+                              const double* dirs, uint32_t n, uint32_t k0, uint32_t k1, double* out_dir, double* out_pdf,
+                              double* out_pdf_dirs, int32_t* out_draws, hipStream_t s) {
+    const uint32_t blocks = (n + 255u) / 256u;
+    if (!blocks) return hipSuccess;
+    if (light_mode(sc).v == 0) return hipErrorInvalidValue;      // no light: no kernel to fall back on
+    using ProbeKernel = void (*)(const DevScene*, const double*, const double*, uint32_t, uint32_t, uint32_t, double*,
+                                 double*, double*, int32_t*);
+    const ProbeKernel k = dispatch([](auto LIST, auto EX) -> ProbeKernel { return k_light_probe<LIST() ? 2 : 1, EX()>; },
+                                   light_mode(sc).v == 2, exact_libm);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, s, scd, points, dirs, n, k0, k1, out_dir, out_pdf, out_pdf_dirs,
+                       out_draws);
     return hipGetLastError();
 }
 // bytes of LDS k_extend_lds needs for the scene's time-0 tree (0 = cannot run)

@@ -70,6 +70,12 @@ hipError_t launch_hit_rays_lds(const DevScene& sc, bool time0, size_t lds, const
 // features added to feat (RT_FEATURE_DOUBLES running sums per image pixel); only nx, ny, inx, iny, npix,
 // spp0, k0, k1 and pixlist of rp are read
 hipError_t launch_features(const DevScene& sc, const RenderParams& rp, uint32_t S, double* feat, hipStream_t s);
+// rt_light_probe: n points (3 doubles each) through the mixture's light sampler and density, point k on the
+// path stream (k0, k1; pixel k, sample 0) from counter 0; dirs / out_pdf_dirs null together; exact_libm: the
+// sphere sampler's sin / cos as the scene's renders take them.  A scene without light sampling is an error.
+hipError_t launch_light_probe(const DevScene& sc, const DevScene* scd, bool exact_libm, const double* points,
+                              const double* dirs, uint32_t n, uint32_t k0, uint32_t k1, double* out_dir, double* out_pdf,
+                              double* out_pdf_dirs, int32_t* out_draws, hipStream_t s);
 // the device fault word: read and clear
 hipError_t take_fault(uint32_t* out);
 // the batched-curve counters: read and clear

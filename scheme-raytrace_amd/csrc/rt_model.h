@@ -47,6 +47,7 @@ struct SceneDesc {
     bool have_cam = false;
     int sky = RT_SKY_GRADIENT;
     int light = -1;                   // rt_set_light_sampling target (-1: off)
+    std::vector<int> lights;          // rt_set_light_list's object ids (empty: none; set: light is -1)
     std::vector<double> ranvec;
     std::vector<int32_t> perm;
     bool have_perlin = false;

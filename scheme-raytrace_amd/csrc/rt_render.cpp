@@ -91,6 +91,11 @@ size_t max_paths(const Context& c, const int lanes) {
     return v < ((size_t)1 << 20) ? ((size_t)1 << 20) : v;
 }
 
+// the libm mode a scene's renders (and rt_light_probe) take under the context's RT_OPT_EXACT_LIBM
+bool scene_exact_libm(const Context& c, const Scene& s) {
+    return c.opt_exact_libm == RT_LIBM_EXACT ||
+           (c.opt_exact_libm == RT_LIBM_AUTO && (s.dev.n_bez > 0 || s.dev.has_noise_tex));
+}
 int lanes_wanted(const Context& c) {   // RT_OPT_LANES: path pools kept in flight (1 = no overlap)
     return c.opt_lanes > 0 ? (int)std::min<int64_t>(c.opt_lanes, kLanes) : 2;
 }
@@ -293,8 +298,7 @@ int render_impl(Scene* s, int nx, int ny, const PixSet& px, int spp_begin, int s
     // C3 (marble) frame rows with the device library's sin / cos were 0.79 % of pixels off by more than 1e-9;
     // exact there costs 1.7 % (profiles/r06/c3_libm/).  The cover scene keeps the device's: exact would cost it
     // 1.4 % (profiles/r06/c2_libm/) for 26 of 15 360 horizon pixels at 256 passes, all within 1e-7
-    const bool exact_libm = c->opt_exact_libm == RT_LIBM_EXACT ||
-                            (c->opt_exact_libm == RT_LIBM_AUTO && (s->dev.n_bez > 0 || s->dev.has_noise_tex));
+    const bool exact_libm = scene_exact_libm(*c, *s);
     // point records for the lambertian queue of the launches the SOLO LDS kernels make (rt_device.h HitPt)
     const bool point_hits = s->point_hits && !point_hits_off();
     uint64_t seq = 0;
@@ -624,6 +628,47 @@ int rt_hit_rays_stream(int scene, const double* rays, int n, uint64_t seed, doub
                                   d_t.as<double>(), d_mat.as<int32_t>(), d_draws.as<int32_t>(), c->stream));
     HIPCHK(hipMemcpyAsync(out_t, d_t.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(out_mat, d_mat.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out_draws, d_draws.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    uint32_t f = 0;
+    HIPCHK(take_fault(&f));
+    if (f) return fail(fault_text(f));
+    return 0;
+}
+
+int rt_light_probe(int scene, int n, const double* points, const double* dirs, uint64_t seed, double* out_dir,
+                   double* out_pdf, double* out_pdf_dirs, int32_t* out_draws) {
+    LOCK_SCENE(s, scene);
+    if (!s->committed) return fail("scene not committed (rt_scene_commit)");
+    if (s->dev.light.type == LIGHT_OFF)
+        return fail("rt_light_probe: the scene has no light sampling (rt_set_light_sampling / rt_set_light_list)");
+    if (n < 0) return fail("rt_light_probe: point count must be >= 0");
+    if (!points || !out_dir || !out_pdf || !out_draws) return fail("rt_light_probe: null pointer");
+    if ((dirs == nullptr) != (out_pdf_dirs == nullptr)) return fail("rt_light_probe: dirs and out_pdf_dirs are null together");
+    CTX_OF(c, s);
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    uint32_t stale = 0;
+    HIPCHK(take_fault(&stale));
+    const size_t n3 = (size_t)n * 3 * sizeof(double), n1 = (size_t)n * sizeof(double);
+    DevBuf d_pts, d_dirs, d_out, d_pdf, d_pdfd, d_draws;
+    HIPCHK(d_pts.ensure(n3));
+    HIPCHK(d_out.ensure(n3));
+    HIPCHK(d_pdf.ensure(n1));
+    HIPCHK(d_draws.ensure((size_t)n * sizeof(int32_t)));
+    HIPCHK(hipMemcpyAsync(d_pts.p, points, n3, hipMemcpyHostToDevice, c->stream));
+    if (dirs) {
+        HIPCHK(d_dirs.ensure(n3));
+        HIPCHK(d_pdfd.ensure(n1));
+        HIPCHK(hipMemcpyAsync(d_dirs.p, dirs, n3, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(launch_light_probe(s->dev, s->d_dev.as<const DevScene>(), scene_exact_libm(*c, *s), d_pts.as<const double>(),
+                              dirs ? d_dirs.as<const double>() : nullptr, (uint32_t)n, (uint32_t)seed, (uint32_t)(seed >> 32),
+                              d_out.as<double>(), d_pdf.as<double>(), dirs ? d_pdfd.as<double>() : nullptr,
+                              d_draws.as<int32_t>(), c->stream));
+    HIPCHK(hipMemcpyAsync(out_dir, d_out.p, n3, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out_pdf, d_pdf.p, n1, hipMemcpyDeviceToHost, c->stream));
+    if (dirs) HIPCHK(hipMemcpyAsync(out_pdf_dirs, d_pdfd.p, n1, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(out_draws, d_draws.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     uint32_t f = 0;

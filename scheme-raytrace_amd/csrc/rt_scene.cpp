@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "rt_build.h"
 #include "rt_host.h"
 
 using namespace rtamd;
@@ -365,13 +366,23 @@ int rt_add_constant_medium(int scene, int boundary, double density, int albedo_t
 }
 int rt_set_light_sampling(int scene, int light_obj) {
     SCENE_OR_FAIL(s, scene);
-    if (light_obj < 0) { s->light = -1; return 0; }
+    if (light_obj < 0) { s->light = -1; s->lights.clear(); return 0; }
     if (check_obj(s, light_obj)) return 1;
     const Obj* L = &s->objs[light_obj];
     while (L->type == O_FLIP) L = &s->objs[L->child];
     if (L->type != O_RECT && L->type != O_SPHERE)
         return fail("rt_set_light_sampling: the light must be a rect or a sphere (optionally flipped)");
     s->light = light_obj;
+    s->lights.clear();                                  // the last of the two setters wins
+    return 0;
+}
+int rt_set_light_list(int scene, const int* objs, int n) {
+    SCENE_OR_FAIL(s, scene);
+    std::vector<int> flat;
+    std::string err;
+    if (flatten_lights(*s, objs, n, flat, err)) return fail(err);   // (the scene is left as it was)
+    s->lights.assign(objs, objs + n);
+    s->light = -1;
     return 0;
 }
 int rt_add_flip_normals(int scene, int child, int* out) {

@@ -26,6 +26,7 @@ RT_OPTIONS = {"lanes": 1, "max_paths": 2, "tail_paths": 3, "tail_div": 4, "tail_
 #: library's sin / cos bit for bit), device (the device library's)
 RT_LIBM = {"auto": 0, "exact": 1, "device": 2}
 RT_COMM_ID_BYTES = 128
+RT_MAX_LIGHTS = 4096
 
 
 class RtStats(ctypes.Structure):
@@ -142,6 +143,9 @@ _SIGNATURES = {
     "rt_set_camera": [ctypes.c_int, _c_double_p],
     "rt_set_sky": [ctypes.c_int, ctypes.c_int],
     "rt_set_light_sampling": [ctypes.c_int, ctypes.c_int],
+    "rt_set_light_list": [ctypes.c_int, _c_int_p, ctypes.c_int],                             # RT_HAS_LIGHT_LIST
+    "rt_light_probe": [ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_uint64, _c_double_p, _c_double_p,
+                       _c_double_p, _c_i32_p],
     "rt_set_perlin_tables": [ctypes.c_int, _c_double_p, _c_i32_p, _c_i32_p, _c_i32_p],
     "rt_scene_commit": [ctypes.c_int, ctypes.c_int],
     "rt_render": [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,

@@ -190,6 +190,11 @@ class GpuBuilder:
     def set_light(self, obj):
         call("rt_set_light_sampling", self.scene, obj)
 
+    def set_lights(self, objs):
+        """rt_set_light_list: the objects (rects, spheres, triangles, flips, lists, meshes) the mixture samples."""
+        arr = (ctypes.c_int * max(1, len(objs)))(*objs)
+        call("rt_set_light_list", self.scene, arr, len(objs))
+
     def set_sky(self, code):
         call("rt_set_sky", self.scene, code)
 
@@ -337,6 +342,28 @@ def hit_rays_stream(scene, rays, seed, ctx=None):
          ctypes.c_uint64(seed & (2**64 - 1)), t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
          m.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), draws.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
     return t, m, draws
+
+
+def light_probe(scene, points, seed, dirs=None, ctx=None):
+    """rt_light_probe: the mixture's light sampler and density for points (n, 3), point k on the path stream
+    (seed, pixel k, sample 0).  Returns (out_dir (n, 3), out_pdf (n,), out_pdf_dirs (n,) or None, draws (n,)):
+    random(point), pdf_value(point, out_dir), pdf_value(point, dirs[k]) and the random numbers consumed."""
+    h = upload(scene, ctx)
+    dp = ctypes.POINTER(ctypes.c_double)
+    p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    n = p.shape[0]
+    d = None
+    if dirs is not None:
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        if d.shape[0] != n:
+            raise ValueError("one direction per point")
+    out_dir, out_pdf = np.zeros((n, 3)), np.zeros(n)
+    out_pdf_dirs = np.zeros(n) if d is not None else None
+    draws = np.zeros(n, dtype=np.int32)
+    call("rt_light_probe", h, n, p.ctypes.data_as(dp), d.ctypes.data_as(dp) if d is not None else None, _u64(seed),
+         out_dir.ctypes.data_as(dp), out_pdf.ctypes.data_as(dp),
+         out_pdf_dirs.ctypes.data_as(dp) if d is not None else None, draws.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    return out_dir, out_pdf, out_pdf_dirs, draws
 
 
 def resolve_u8(accum, nx, ny, sample_count):

@@ -284,7 +284,7 @@ class Scene:
     (the reference's module-level +ranvec+/+perm-*+, perlin.scm:32-36).
     """
 
-    def __init__(self, obj_list, camera, sky_function, perlin=None, light=None):
+    def __init__(self, obj_list, camera, sky_function, perlin=None, light=None, lights=None):
         self.obj_list = tuple(obj_list)
         for o in self.obj_list:
             _need(o, Hitable, "make-scene obj-list element")
@@ -302,6 +302,17 @@ class Scene:
             if inner.kind not in ("rect", "sphere"):
                 raise ValueError("light sampling needs a rect or a sphere (optionally flipped)")
         self.light = light
+        # the mixture over a list of lights (include/rt.h, "light lists"; restated in rtamd.lights): rects,
+        # spheres, triangles, flips of these, meshes.  The oracle does not know it.
+        if lights is not None:
+            if light is not None:
+                raise ValueError("make-scene: give light or lights, not both")
+            from . import lights as _lights
+            lights = tuple(lights)
+            for o in lights:
+                _need(o, Hitable, "light-list element")
+            _lights.flatten(lights)                 # raises ValueError for what rt_set_light_list refuses
+        self.lights = lights
         self._handles = {}
 
     def uses_perlin(self):
@@ -322,13 +333,17 @@ class Scene:
         return False
 
 
-def make_scene(obj_list, camera, sky_function, perlin=None, light=None):
+def make_scene(obj_list, camera, sky_function, perlin=None, light=None, lights=None):
     """g:make-scene (geometry.scm:52).  ``light`` (extension, pdf.scm): an
     object of obj_list (a rect or sphere, possibly flipped) that lambertian
-    bounces sample through the light/cosine mixture pdf."""
+    bounces sample through the light/cosine mixture pdf.  ``lights``: a list
+    of such objects, triangles and meshes instead (rt_set_light_list): the
+    mixture samples one of them, picked uniformly.  An empty list is refused
+    (ValueError) on purpose: no light list is ``lights=None``; the ABI's
+    n == 0 ("sampling off") is reached through GpuBuilder.set_lights([])."""
     if not isinstance(sky_function, SkyFunction):
         raise TypeError("make-scene: sky function must be sky_color or black (got %r)" % (sky_function,))
-    return Scene(obj_list, camera, sky_function, perlin, light)
+    return Scene(obj_list, camera, sky_function, perlin, light, lights)
 
 
 def _need(x, cls, what):
@@ -427,6 +442,11 @@ def emit(scene, b):
     world = b.list(ids)
     if getattr(scene, "light", None) is not None:
         b.set_light(obj(scene.light))
+    if getattr(scene, "lights", None) is not None:
+        if not hasattr(b, "set_lights"):
+            raise NotImplementedError("light lists are not restated in %s (only the GPU builder takes them; "
+                                      "rtamd.lights is their NumPy restatement)" % type(b).__name__)
+        b.set_lights([obj(o) for o in scene.lights])
     b.set_camera(scene.camera.slots())
     b.set_sky(scene.sky_function.code)
     if scene.uses_perlin():

@@ -174,6 +174,13 @@ def cornell_mesh(nx, ny):
     return g.make_scene(objs, cornell_camera_for(nx, ny), g.sky_color)
 
 
+def cornell_mesh_lights(nx, ny):
+    """cornell_mesh sampling its own lamp: the third mesh (the ceiling light's two triangles) as the light
+    list (include/rt.h, "light lists"), so lambertian bounces take the light / cosine mixture."""
+    sc = cornell_mesh(nx, ny)
+    return g.make_scene(sc.obj_list, sc.camera, sc.sky_function, lights=[sc.obj_list[2]])
+
+
 def cornell_image_textures(floor_size=(64, 64), wall_size=(32, 32)):
     """cornell_image's two images, generated from formulas: the floor a grid of warm tiles with dark joints,
     the back wall a smooth two-way colour ramp.  Returns (floor, wall) image textures."""
@@ -476,6 +483,7 @@ SCENES = {
     "cornell_image": cornell_image,
     "cornell_lifted": cornell_lifted,
     "cornell_mesh": cornell_mesh,
+    "cornell_mesh_lights": cornell_mesh_lights,
     "klein": klein_scene,
     "cornell_klein": cornell_klein,
     "curves": cornell_curves,
