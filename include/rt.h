@@ -432,6 +432,56 @@ int rt_hit_rays_walk(int scene, int walk, int n, const double* rays, double* out
 int rt_hit_rays_stream(int scene, const double* rays, int n, uint64_t seed, double* out_t, int32_t* out_mat,
                        int32_t* out_draws);
 
+/* ---- one wavefront iteration on a caller's path states (RT_HAS_STEP_PROBE; a test probe) ---------------
+ * rt_step_rays builds the path state of n paths, runs ONE iteration of the render's wavefront on it through
+ * the render's own launchers, and reads everything back.  Opt-in: nothing above changes, RT_ABI_VERSION
+ * stays 7; test RT_HAS_STEP_PROBE.
+ *
+ * Record k (host memory): rays[7k..] = {ox, oy, oz, dx, dy, dz, time}, T_in[3k..] its throughput, ctr_in[k]
+ * its draw counter, pix[k] its pixel key (pix null: pix[k] = k).  Record k draws from the Philox stream of
+ * (seed, pix[k], smp) from draw ctr_in[k] on (the oracle's orc_step with the same numbers).
+ *
+ * The state.  depth 0: the raygen layout (ray, time, counter; slot k = work id k, contiguous); the
+ * throughput of a depth-0 path is 1 by construction, so any other T_in is refused.  depth >= 1: the
+ * survivor layout a shade kernel leaves behind, PathRec{T, wid = k, rng} in the 8 sharded queues (record k
+ * in shard (k / 256) % 8, the shards' counts in the previous iteration's counter row) with shard capacity,
+ * counter rows and hit-queue strides computed as a render of n paths computes them; a scattered ray has time
+ * +0.0, so any other time is refused.  RenderParams: npix = n, pixlist = pix, spp0 = smp, B = n, the libm
+ * mode the scene's renders take (RT_OPT_EXACT_LIBM).  The sample buffer is pre-filled with the NaN pattern
+ * 0x7FF8DEAD5CA77E12 in every double (RT_STEP_SENTINEL): a slot that still holds it was not written.
+ *
+ * extend: RT_STEP_EXTEND_HBM = launch_extend (k_extend<F>, HitRec queues, depth0 = (depth == 0));
+ * RT_STEP_EXTEND_LDS = launch_extend_lds (depth >= 1 and rt_scene_info.extend_lds_bytes > 0 only), which
+ * queues lambertian hits as point records exactly when a render's would (rt_scene_point_hits).  Scenes whose
+ * renders take the persistent curve kernel (every curve in the world BVH, no media, no Klein set) are
+ * refused.  Scenes with media are allowed: the hit test draws, and the shade continues from its counter.
+ *
+ * mode RT_STEP_STEP: after the extend, launch_shade for every material type of the scene.  Outputs per
+ * record k: out_status[k] = (times wid k appears among the survivors) | RT_STEP_WROTE if its sample slot no
+ * longer holds the sentinel; out_color[3k..] the slot's three doubles; for a survivor (the last one found)
+ * out_ray[6k..] = {o, d}, out_T[3k..], out_ctr[k]; out_t[k] / out_mat[k] = the queued hit's t and material
+ * id, out_mat -1 (t 0) for a record in no hit queue, t NaN for a point record (it carries no t).
+ * *out_survivors = the sum of the device's survivor counters.  out_inst[8m..8m+5] for material type m =
+ * {launched, TL, LS, LL, EX, PT} of the k_shade instance launch_shade took (all 0 when the scene has no such
+ * material).
+ * mode RT_STEP_TAIL: launch_finish on the same state at `depth` instead of extend + shade; out_color /
+ * out_status as above (no survivors), out_inst[0..5] = {1, F, TL, LS, SOLO, EX} of the k_finish instance;
+ * the other outputs are left alone.
+ * The instance tuples come from the selection functions launch_shade / launch_finish themselves call.
+ *
+ * Refused before any device work: null pointers (pix excepted), n < 0, depth outside 0..100, an unknown
+ * extend or mode, an uncommitted scene, RT_STEP_EXTEND_LDS at depth 0 or in a scene without that kernel.
+ * n = 0 returns at once with *out_survivors = 0 and out_inst cleared. */
+#define RT_HAS_STEP_PROBE 1
+enum { RT_STEP_EXTEND_HBM = 0, RT_STEP_EXTEND_LDS = 1 };
+enum { RT_STEP_STEP = 0, RT_STEP_TAIL = 1 };
+enum { RT_STEP_WROTE = 256 };
+#define RT_STEP_SENTINEL 0x7FF8DEAD5CA77E12ull
+int rt_step_rays(int scene, int n, const double* rays, const double* T_in, const uint32_t* ctr_in,
+                 const uint32_t* pix /* nullable */, uint64_t seed, uint32_t smp, int depth, int extend, int mode,
+                 int32_t* out_status, double* out_color, double* out_ray, double* out_T, uint32_t* out_ctr,
+                 double* out_t, int32_t* out_mat, int32_t* out_inst /* 32 */, uint32_t* out_survivors);
+
 /* converge's subdivision depth (bezier.scm:179-193) as the curve kernels compute it (bez_maxd): for n
  * curves given in ray space (cps = n x 12 doubles, the control points after bezier-transform) and 8 eps
  * each (eps = width / 20), out_depth[i] = ceiling((log z) / (log 4)) with z = sqrt(2) n (n-1) l0 / (8 eps),

@@ -60,6 +60,7 @@ def lib():
             "orc_set_camera": ([V, _dp], None),
             "orc_set_sky": ([V, ctypes.c_int], None),
             "orc_set_light_sampling": ([V, ctypes.c_int], None),
+            "orc_set_light_list": ([V, ctypes.POINTER(ctypes.c_int), ctypes.c_int], ctypes.c_int),
             "orc_light_pdf_value": ([V, _dp, _dp], ctypes.c_double),
             "orc_set_world": ([V, ctypes.c_int], None),
             "orc_set_perlin_tables": ([V, _dp, _ip, _ip, _ip], None),
@@ -87,6 +88,10 @@ def lib():
             "orc_onb": ([_dp, _dp], None),
             "orc_hit_world": ([V, _dp, _dp, ctypes.c_double, _dp], ctypes.c_int),
             "orc_set_bvh_flat": ([V, ctypes.c_int], None),
+            "orc_step": ([V, _dp, _dp, ctypes.c_double, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                          ctypes.c_uint32, _dp], ctypes.c_uint32),
+            "orc_color_from": ([V, _dp, _dp, ctypes.c_double, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
+                                ctypes.c_uint32, ctypes.c_uint32, _dp], None),
             "orc_trace_sample": ([V, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
                                   ctypes.c_uint32, _dp, ctypes.c_int], ctypes.c_int),
         }
@@ -108,6 +113,7 @@ class OracleScene:
     def __init__(self):
         self.L = lib()
         self.s = self.L.orc_scene_new()
+        self.spheres = []                   # the ids sphere() returned, in order (tests name lights by them)
 
     def __del__(self):
         try:
@@ -140,7 +146,8 @@ class OracleScene:
         return self.L.orc_add_material_diffuse_light(self.s, tex)
 
     def sphere(self, c, r, mat):
-        return self.L.orc_add_sphere(self.s, _dv(c), r, mat)
+        self.spheres.append(self.L.orc_add_sphere(self.s, _dv(c), r, mat))
+        return self.spheres[-1]
 
     def moving_sphere(self, c0, c1, t0, t1, r, mat):
         return self.L.orc_add_moving_sphere(self.s, _dv(c0), _dv(c1), t0, t1, r, mat)
@@ -186,7 +193,16 @@ class OracleScene:
         self.L.orc_set_camera(self.s, _dv(slots))
 
     def set_light(self, obj):
+        self.light_obj = obj
         self.L.orc_set_light_sampling(self.s, obj)
+
+    def set_light_list(self, objs):
+        """The mixture over a list of rects / spheres (include/rt.h, "light lists": the index draw, 1/m weights).
+        Not `set_lights`: rtamd.scene.emit hands light lists to the GPU builder only, since the oracle restates
+        neither triangles nor lights outside the world; tests that know their list call this themselves."""
+        arr = (ctypes.c_int * len(objs))(*objs)
+        if self.L.orc_set_light_list(self.s, arr, len(objs)) != 0:
+            raise ValueError("the oracle takes a list of 1 to 16 rects / spheres")
 
     def light_pdf_value(self, o, v):
         return self.L.orc_light_pdf_value(self.s, _dv(o), _dv(v))
@@ -232,6 +248,31 @@ class OracleScene:
         n = self.L.orc_trace_sample(self.s, nx, ny, x, y, seed, smp, out.ctypes.data_as(_dp), cap)
         return out[:13 * n].reshape(n, 13)
 
+    def step(self, rays, depth, seed, smp, pix=None, ctr_in=None):
+        """orc_step on rays (n, 7) (origin, direction, time): one segment of each path at `depth`, record k on
+        the stream of (seed, pix[k] (default k), smp) from draw ctr_in[k] (default 0).  Returns (rows (n, 24),
+        counters (n,) uint32); the columns are STEP_* below."""
+        r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 7)
+        n = r.shape[0]
+        rows = np.zeros((n, 24))
+        ctr = np.zeros(n, dtype=np.uint32)
+        for k in range(n):
+            ctr[k] = self.L.orc_step(self.s, r[k, 0:3].ctypes.data_as(_dp), r[k, 3:6].ctypes.data_as(_dp), r[k, 6],
+                                     int(depth), seed & (2**64 - 1), int(k if pix is None else pix[k]), int(smp),
+                                     int(0 if ctr_in is None else ctr_in[k]), rows[k].ctypes.data_as(_dp))
+        return rows, ctr
+
+    def color_from(self, rays, depth, seed, smp, pix=None, ctr_in=None):
+        """orc_color_from: color() started from each path state of `step`'s arguments; (n, 3)."""
+        r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 7)
+        n = r.shape[0]
+        out = np.zeros((n, 3))
+        for k in range(n):
+            self.L.orc_color_from(self.s, r[k, 0:3].ctypes.data_as(_dp), r[k, 3:6].ctypes.data_as(_dp), r[k, 6],
+                                  int(depth), seed & (2**64 - 1), int(k if pix is None else pix[k]), int(smp),
+                                  int(0 if ctr_in is None else ctr_in[k]), out[k].ctypes.data_as(_dp))
+        return out
+
     def hit_world(self, o, d, time=0.0):
         out = (ctypes.c_double * 8)()
         ok = self.L.orc_hit_world(self.s, _dv(o), _dv(d), time, out)
@@ -247,6 +288,13 @@ class OracleScene:
         out = (ctypes.c_double * 3)()
         self.L.orc_tex_value(self.s, tex, _dv(p), out)
         return tuple(out)
+
+
+#: orc_step's row: kind (0 the path ends with colour L, 1 it scatters), hit?, t, material id, material type,
+#: L, the scattered ray, the weight's parts a and ipdf (rt_oracle.c segment_t), the hit point and normal
+STEP_KIND, STEP_HIT, STEP_T, STEP_MAT, STEP_MTYPE = 0, 1, 2, 3, 4
+STEP_L, STEP_O, STEP_D, STEP_A, STEP_IPDF, STEP_P, STEP_N = slice(5, 8), slice(8, 11), slice(11, 14), slice(14, 17), 17, \
+    slice(18, 21), slice(21, 24)
 
 
 def build_scene(scene):

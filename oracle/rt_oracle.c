@@ -149,6 +149,7 @@ typedef struct {
     double cam[24];
     int sky, world;
     int light;                          /* light-sampling target object (-1: off), pdf.scm extension */
+    int lights[16], nlights;            /* a list of such targets (orc_set_light_list; 0: the single one) */
     v3 ranvec[256];
     int perm_x[256], perm_y[256], perm_z[256];
     int have_perlin;
@@ -323,7 +324,17 @@ void orc_set_camera(orc_scene* s, const double cam[24]) { memcpy(s->cam, cam, si
  * semantics the trees reproduce); 0 (default): use the trees. */
 void orc_set_bvh_flat(orc_scene* s, int flat) { s->bvh_flat = flat; }
 void orc_set_sky(orc_scene* s, int sky) { s->sky = sky; }
-void orc_set_light_sampling(orc_scene* s, int obj) { s->light = obj; }
+void orc_set_light_sampling(orc_scene* s, int obj) { s->light = obj; s->nlights = 0; }
+/* The mixture over a list of m >= 1 rects / spheres (flips allowed), the rule of include/rt.h "light lists":
+ * pdf_value = sum of (1/m) * pdf_i, random = one index draw when m > 1, then random_i.  Returns 0, or -1 for
+ * a list this restatement does not take (empty, longer than 16). */
+int orc_set_light_list(orc_scene* s, const int* objs, int n) {
+    if (n < 1 || n > 16) return -1;
+    for (int i = 0; i < n; ++i) s->lights[i] = objs[i];
+    s->nlights = n;
+    s->light = objs[0];
+    return 0;
+}
 void orc_set_world(orc_scene* s, int world) { s->world = world; }
 void orc_set_perlin_tables(orc_scene* s, const double* ranvec, const int32_t* px, const int32_t* py,
                            const int32_t* pz) {
@@ -1178,14 +1189,14 @@ static v3 sky(const orc_scene* s, ray_t r) {
  * mixture (light, cosine) for lambertian bounces.  Scheme semantics are kept:
  * onb `local` is the syntax-rules macro, so a sampler passed to it runs three
  * times (Q29).  Not pinned against the reference (it has no such path). */
-static const orc_obj* light_obj(const orc_scene* s) {
-    const orc_obj* o = &s->obj[s->light];
+static const orc_obj* light_obj(const orc_scene* s, int id) {
+    const orc_obj* o = &s->obj[id];
     while (o->type == OBJ_FLIP) o = &s->obj[o->child];
     return o;
 }
 /* g:pdf-value: density of direction v from origin o */
-static double light_pdf_value(const orc_scene* s, v3 o, v3 v) {
-    const orc_obj* L = light_obj(s);
+static double light_pdf_value_of(const orc_scene* s, int id, v3 o, v3 v) {
+    const orc_obj* L = light_obj(s, id);
     hitrec rec;
     ray_t r = {o, v, 0.0};
     if (L->type == OBJ_RECT) {
@@ -1201,6 +1212,12 @@ static double light_pdf_value(const orc_scene* s, v3 o, v3 v) {
     double solid_angle = 2 * ORC_PI * (1 - cos_theta_max);
     return 1 / solid_angle;
 }
+static double light_pdf_value(const orc_scene* s, v3 o, v3 v) {
+    if (s->nlights == 0) return light_pdf_value_of(s, s->light, o, v);
+    double w = 1.0 / (double)s->nlights, sum = 0.0;
+    for (int i = 0; i < s->nlights; ++i) sum = sum + w * light_pdf_value_of(s, s->lights[i], o, v);
+    return sum;
+}
 static v3 random_to_sphere(double radius, double distance_squared, orc_rng* g) {
     double r1 = orc_random_real(g);
     double r2 = orc_random_real(g);
@@ -1211,8 +1228,8 @@ static v3 random_to_sphere(double radius, double distance_squared, orc_rng* g) {
     return V(x, y, z);
 }
 /* g:random: a direction from o toward the light */
-static v3 light_random(const orc_scene* s, v3 o, orc_rng* g) {
-    const orc_obj* L = light_obj(s);
+static v3 light_random_of(const orc_scene* s, int id, v3 o, orc_rng* g) {
+    const orc_obj* L = light_obj(s, id);
     if (L->type == OBJ_RECT) {
         double a = L->a0 + orc_random_real(g) * (L->a1 - L->a0);
         double b = L->b0 + orc_random_real(g) * (L->b1 - L->b0);
@@ -1227,6 +1244,16 @@ static v3 light_random(const orc_scene* s, v3 o, orc_rng* g) {
     double z = random_to_sphere(L->r, distance_squared, g).z;
     return onb_local(uvw, V(x, y, z));
 }
+static v3 light_random(const orc_scene* s, v3 o, orc_rng* g) {
+    if (s->nlights == 0) return light_random_of(s, s->light, o, g);
+    int i = 0;
+    if (s->nlights > 1) {
+        double r = orc_random_real(g);
+        i = (int)(r * (double)s->nlights);
+        if (i > s->nlights - 1) i = s->nlights - 1;
+    }
+    return light_random_of(s, s->lights[i], o, g);
+}
 /* make-cosine-pdf's value (pdf.scm:19-23) */
 static double cosine_pdf_value(onb_t uvw, v3 dir) {
     double cosine = vdot(vunit(dir), uvw.w);
@@ -1238,12 +1265,30 @@ double orc_light_pdf_value(const orc_scene* s, const double o[3], const double v
 
 typedef struct { uint64_t segments; int max_depth; } orc_counters;
 
-/* main.scm:100-121 — recursive colour */
 /* debugging aid (orc_trace_sample): per segment o, d, hit?, t, p, mat, draw counter */
 static __thread double* tl_trace;
 static __thread int tl_trace_n, tl_trace_cap;
 
-static v3 color(const orc_scene* s, ray_t r, int depth, orc_rng* g, orc_counters* cnt) {
+/* One segment of a path: the closest hit with the stream attached, then what main.scm's color does with
+ * it before it recurses.  SEG_DONE: the path ends here with colour L (sky, emission, or black for an
+ * absorbed, pdf-less or depth-capped bounce).  SEG_SCATTER: it goes on along `next`, and the colour is
+ *   lambertian  (0,0,0) + ((a (*) L_next) * ipdf)     a = att*spdf, ipdf = 1/pdf
+ *   metal       a (*) L_next                           a = att
+ *   dielectric  (1,1,1) (*) L_next
+ * of the next segment's L_next (color() below forms it; orc_step hands the parts out). */
+enum { SEG_DONE = 0, SEG_SCATTER = 1 };
+typedef struct {
+    int kind, hit, mtype;               /* mtype: the hit material's type (-1: miss) */
+    hitrec rec;                         /* valid when hit */
+    v3 L;                               /* SEG_DONE */
+    ray_t next; v3 a; double ipdf;      /* SEG_SCATTER */
+} segment_t;
+static void seg_done(segment_t* sg, v3 L) { sg->kind = SEG_DONE; sg->L = L; }
+static void seg_scatter(segment_t* sg, ray_t next, v3 a, double ipdf) {
+    sg->kind = SEG_SCATTER; sg->next = next; sg->a = a; sg->ipdf = ipdf;
+}
+
+static void segment(const orc_scene* s, ray_t r, int depth, orc_rng* g, orc_counters* cnt, segment_t* sg) {
     hitrec rec;
     const orc_obj* w = &s->obj[s->world];
     cnt->segments++;
@@ -1257,8 +1302,10 @@ static v3 color(const orc_scene* s, ray_t r, int depth, orc_rng* g, orc_counters
         q[6] = hit; q[7] = hit ? rec.t : 0; q[8] = hit ? rec.p.x : 0; q[9] = hit ? rec.p.y : 0;
         q[10] = hit ? rec.p.z : 0; q[11] = hit ? rec.mat : -1; q[12] = g->ctr;
     }
-    if (!hit) return sky(s, r);
+    sg->hit = hit; sg->mtype = -1;
+    if (!hit) { seg_done(sg, sky(s, r)); return; }
     const orc_mat* m = &s->mat[rec.mat];
+    sg->rec = rec; sg->mtype = m->type;
     switch (m->type) {
     case MAT_LAMBERTIAN: {                                              /* material.scm:24-39 */
         if (s->light >= 0) {
@@ -1277,16 +1324,17 @@ static v3 color(const orc_scene* s, ray_t r, int depth, orc_rng* g, orc_counters
             double pdf_val = 0.5 * light_pdf_value(s, rec.p, dir) + 0.5 * cosine_pdf_value(uvw, dir);
             /* a direction neither pdf can produce (a light sample that grazes
              * past the light, below the surface) ends the path: no 0 * inf */
-            if (!(pdf_val > 0)) return V(0, 0, 0);
+            if (!(pdf_val > 0)) { seg_done(sg, V(0, 0, 0)); return; }
             v3 att = tex_value(s, m->tex, 0, 0, rec.p);
             if (depth < ORC_MAX_DEPTH) {
                 double cosine = vdot(rec.n, vunit(scattered.d));
                 if (cosine < 0) cosine = 0;
                 double spdf = cosine / ORC_PI;
-                v3 L = color(s, scattered, depth + 1, g, cnt);
-                return vadd(V(0, 0, 0), vscale(vmul(vscale(att, spdf), L), 1 / pdf_val));
+                seg_scatter(sg, scattered, vscale(att, spdf), 1 / pdf_val);
+                return;
             }
-            return V(0, 0, 0);
+            seg_done(sg, V(0, 0, 0));
+            return;
         }
         onb_t uvw = make_onb_from_w(rec.n);
         /* (local uvw (random-cosine-direction)) — `local` is a syntax-rules
@@ -1304,11 +1352,12 @@ static v3 color(const orc_scene* s, ray_t r, int depth, orc_rng* g, orc_counters
             double cosine = vdot(rec.n, vunit(scattered.d));
             if (cosine < 0) cosine = 0;
             double spdf = cosine / ORC_PI;
-            v3 L = color(s, scattered, depth + 1, g, cnt);
             /* emitted (0,0,0) + ((att*spdf) (*) L) * (1/pdf) */
-            return vadd(V(0, 0, 0), vscale(vmul(vscale(att, spdf), L), 1 / pdf));
+            seg_scatter(sg, scattered, vscale(att, spdf), 1 / pdf);
+            return;
         }
-        return V(0, 0, 0);
+        seg_done(sg, V(0, 0, 0));
+        return;
     }
     case MAT_METAL: {                                                   /* material.scm:45-57 (R2) */
         v3 reflected = reflect(vunit(r.d), rec.n);
@@ -1317,9 +1366,11 @@ static v3 color(const orc_scene* s, ray_t r, int depth, orc_rng* g, orc_counters
         v3 att = tex_value(s, m->tex, 0, 0, rec.p);
         if (depth < ORC_MAX_DEPTH && valid) {
             ray_t scattered = {rec.p, dir, 0.0};
-            return vmul(att, color(s, scattered, depth + 1, g, cnt));
+            seg_scatter(sg, scattered, att, 1.0);
+            return;
         }
-        return V(0, 0, 0);
+        seg_done(sg, V(0, 0, 0));
+        return;
     }
     case MAT_DIELECTRIC: {                                              /* material.scm:76-101 (R2) */
         double ref_idx = m->ref_idx;
@@ -1334,15 +1385,69 @@ static v3 color(const orc_scene* s, ray_t r, int depth, orc_rng* g, orc_counters
         ray_t scattered;
         scattered.o = rec.p; scattered.time = 0.0;
         scattered.d = (orc_random_real(g) < reflect_prob) ? reflected : refracted;
-        if (depth < ORC_MAX_DEPTH) return vmul(V(1, 1, 1), color(s, scattered, depth + 1, g, cnt));
-        return V(0, 0, 0);
+        if (depth < ORC_MAX_DEPTH) { seg_scatter(sg, scattered, V(1, 1, 1), 1.0); return; }
+        seg_done(sg, V(0, 0, 0));
+        return;
     }
     case MAT_DIFFUSE_LIGHT:                                             /* material.scm:103-111 */
-        if (vdot(rec.n, r.d) < 0.0) return tex_value(s, m->tex, rec.u, rec.v, rec.p);
-        return V(0, 0, 0);
+        if (vdot(rec.n, r.d) < 0.0) { seg_done(sg, tex_value(s, m->tex, rec.u, rec.v, rec.p)); return; }
+        seg_done(sg, V(0, 0, 0));
+        return;
     }
-    return V(0, 0, 0);
+    seg_done(sg, V(0, 0, 0));
 }
+
+/* main.scm:100-121 — recursive colour: a segment, and for a scattered ray the colour it brings back */
+static v3 color(const orc_scene* s, ray_t r, int depth, orc_rng* g, orc_counters* cnt) {
+    segment_t sg;
+    segment(s, r, depth, g, cnt, &sg);
+    if (sg.kind == SEG_DONE) return sg.L;
+    v3 L = color(s, sg.next, depth + 1, g, cnt);
+    if (sg.mtype == MAT_LAMBERTIAN) return vadd(V(0, 0, 0), vscale(vmul(sg.a, L), sg.ipdf));
+    return vmul(sg.a, L);                                    /* metal: att; dielectric: (1,1,1) */
+}
+
+/* One segment from a given path state (tests): ray (o, d, time) at `depth` on the stream of (seed, pix, smp)
+ * from draw ctr_in.  out[24]: 0 kind (SEG_*), 1 hit?, 2 t, 3 material id (-1: miss), 4 material type (-1),
+ * 5-7 L (SEG_DONE), 8-10 next origin, 11-13 next direction, 14-16 a, 17 ipdf (SEG_SCATTER; see segment_t),
+ * 18-20 hit point, 21-23 normal.  Returns the draw counter after the segment. */
+uint32_t orc_step(const orc_scene* s, const double o[3], const double d[3], double time, int depth, uint64_t seed,
+                  uint32_t pix, uint32_t smp, uint32_t ctr_in, double out[24]) {
+    scene_prepare((orc_scene*)s);
+    orc_rng g = {(uint32_t)seed, (uint32_t)(seed >> 32), pix, smp, ctr_in};
+    orc_counters cnt = {0, 0};
+    ray_t r = {V(o[0], o[1], o[2]), V(d[0], d[1], d[2]), time};
+    segment_t sg;
+    memset(&sg, 0, sizeof sg);
+    segment(s, r, depth, &g, &cnt, &sg);
+    memset(out, 0, 24 * sizeof(double));
+    out[0] = sg.kind; out[1] = sg.hit; out[3] = -1; out[4] = sg.mtype;
+    if (sg.hit) {
+        out[2] = sg.rec.t; out[3] = sg.rec.mat;
+        out[18] = sg.rec.p.x; out[19] = sg.rec.p.y; out[20] = sg.rec.p.z;
+        out[21] = sg.rec.n.x; out[22] = sg.rec.n.y; out[23] = sg.rec.n.z;
+    }
+    if (sg.kind == SEG_DONE) {
+        out[5] = sg.L.x; out[6] = sg.L.y; out[7] = sg.L.z;
+    } else {
+        out[8] = sg.next.o.x; out[9] = sg.next.o.y; out[10] = sg.next.o.z;
+        out[11] = sg.next.d.x; out[12] = sg.next.d.y; out[13] = sg.next.d.z;
+        out[14] = sg.a.x; out[15] = sg.a.y; out[16] = sg.a.z; out[17] = sg.ipdf;
+    }
+    return g.ctr;
+}
+
+/* color() started from a given path state (tests) */
+void orc_color_from(const orc_scene* s, const double o[3], const double d[3], double time, int depth, uint64_t seed,
+                    uint32_t pix, uint32_t smp, uint32_t ctr_in, double out[3]) {
+    scene_prepare((orc_scene*)s);
+    orc_rng g = {(uint32_t)seed, (uint32_t)(seed >> 32), pix, smp, ctr_in};
+    orc_counters cnt = {0, 0};
+    ray_t r = {V(o[0], o[1], o[2]), V(d[0], d[1], d[2]), time};
+    v3 c = color(s, r, depth, &g, &cnt);
+    out[0] = c.x; out[1] = c.y; out[2] = c.z;
+}
+
 
 /* camera.scm:80-92 — get-ray */
 static ray_t get_ray(const double* cam, double s_, double t_, orc_rng* g) {

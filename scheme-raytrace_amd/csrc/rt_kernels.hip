@@ -3778,21 +3778,38 @@ static UpTo<2> light_mode(const DevScene& sc) {
 // (bounce_cos_sin: RT_OPT_EXACT_LIBM, by default in scenes with curves).  Only lambertian scatter uses the
 // light mixture and draws directions; the dielectric attenuation is constant 1, so it has no texture levels
 // pt: the lambertian queue holds point records (point_hits_scene: no light mixture, no image textures)
-static ShadeKernel shade_kernel(const int mat, const DevScene& sc, const RenderParams& rp, const bool ll, const bool pt) {
-    const TexLevel tl{scene_tex_level(sc)};
+constexpr size_t kShadeLeafLds = 32768;      // stage the leaf records when they fit (256 leaves)
+// the instance launch_shade takes for material `mat` (rt_launch.h ShadeInst); pt: the launch that filled the
+// queues wrote point records (only the lambertian queue holds them)
+ShadeInst shade_instance(const int mat, const DevScene& sc, const RenderParams& rp, const bool pt) {
+    const bool ll = (size_t)sc.n_leaves * sizeof(LeafInfo) <= kShadeLeafLds;
+    const int tl = scene_tex_level(sc);
+    const bool ex = rp.exact_libm != 0;
     switch (mat) {
     case MAT_LAMBERTIAN:
-        if (pt)
-            return dispatch([](auto TL, auto LL, auto EX) -> ShadeKernel { return k_shade<MAT_LAMBERTIAN, TL(), false, LL(), EX(), true>; },
-                          UpTo<kTexPerlin>{tl.v}, ll, rp.exact_libm != 0);
-        return dispatch([](auto TL, auto LS, auto LL, auto EX) -> ShadeKernel { return k_shade<MAT_LAMBERTIAN, TL(), LS(), LL(), EX()>; },
-                      tl, light_mode(sc), ll, rp.exact_libm != 0);
-    case MAT_METAL:
-        return dispatch([](auto TL, auto LL) -> ShadeKernel { return k_shade<MAT_METAL, TL(), false, LL(), false>; }, tl, ll);
+        if (pt) return ShadeInst{tl < kTexPerlin ? tl : kTexPerlin, 0, ll, ex, true};
+        return ShadeInst{tl, light_mode(sc).v, ll, ex, false};
     case MAT_DIELECTRIC:
-        return ll ? k_shade<MAT_DIELECTRIC, kTexPlain, false, true, false> : k_shade<MAT_DIELECTRIC, kTexPlain, false, false, false>;
+        return ShadeInst{kTexPlain, 0, ll, false, false};
+    default:                                         // metal, diffuse light
+        return ShadeInst{tl, 0, ll, false, false};
+    }
+}
+static ShadeKernel shade_kernel(const int mat, const ShadeInst& si) {
+    const TexLevel tl{si.tl};
+    switch (mat) {
+    case MAT_LAMBERTIAN:
+        if (si.pt)
+            return dispatch([](auto TL, auto LL, auto EX) -> ShadeKernel { return k_shade<MAT_LAMBERTIAN, TL(), false, LL(), EX(), true>; },
+                          UpTo<kTexPerlin>{si.tl}, si.ll, si.ex);
+        return dispatch([](auto TL, auto LS, auto LL, auto EX) -> ShadeKernel { return k_shade<MAT_LAMBERTIAN, TL(), LS(), LL(), EX()>; },
+                      tl, UpTo<2>{si.ls}, si.ll, si.ex);
+    case MAT_METAL:
+        return dispatch([](auto TL, auto LL) -> ShadeKernel { return k_shade<MAT_METAL, TL(), false, LL(), false>; }, tl, si.ll);
+    case MAT_DIELECTRIC:
+        return si.ll ? k_shade<MAT_DIELECTRIC, kTexPlain, false, true, false> : k_shade<MAT_DIELECTRIC, kTexPlain, false, false, false>;
     default:
-        return dispatch([](auto TL, auto LL) -> ShadeKernel { return k_shade<MAT_DIFFUSE_LIGHT, TL(), false, LL(), false>; }, tl, ll);
+        return dispatch([](auto TL, auto LL) -> ShadeKernel { return k_shade<MAT_DIFFUSE_LIGHT, TL(), false, LL(), false>; }, tl, si.ll);
     }
 }
 // the texture level of the tail's instance: scenes with curves, media or Kleinian sets carry every material's
@@ -3803,16 +3820,13 @@ static int finish_tex_level(const DevScene& sc) {
     const int tl = scene_tex_level(sc);
     return scene_features(sc).f > 0 && tl < kTexPerlin ? kTexPerlin : tl;
 }
-static FinishKernel finish_kernel(const DevScene& sc, const RenderParams& rp, const bool solo) {
-    const FeatSet f = scene_features(sc);
-    const int tl = finish_tex_level(sc);
-    const bool ex = rp.exact_libm != 0;
-    if (f.f > 0)                                     // (every such instance carries the mixture: the single light's, or the list's)
+static FinishKernel finish_kernel(const FinishInst& fi) {
+    if (fi.f > 0)                                    // (every such instance carries the mixture: the single light's, or the list's)
         return dispatch([](auto F, auto LIST, auto IMG, auto EX) -> FinishKernel {
             return k_finish<F(), IMG() ? kTexImage : kTexPerlin, LIST() ? 2 : 1, false, EX()>;
-        }, f, light_mode(sc).v == 2, tl == kTexImage, ex);
+        }, FeatSet{fi.f}, fi.ls == 2, fi.tl == kTexImage, fi.ex);
     return dispatch([](auto TL, auto LS, auto SOLO, auto EX) -> FinishKernel { return k_finish<0, TL(), LS(), SOLO(), EX()>; },
-                  TexLevel{tl}, light_mode(sc), solo, ex);
+                  TexLevel{fi.tl}, UpTo<2>{fi.ls}, fi.solo, fi.ex);
 }
 static FeaturesKernel features_kernel(const DevScene& sc) {
     return dispatch([](auto F, auto TL) -> FeaturesKernel { return k_features<F(), TL()>; },
@@ -3974,7 +3988,6 @@ hipError_t launch_hit_rays_lds(const DevScene& sc, bool time0, size_t lds, const
     hipLaunchKernelGGL(k, dim3(blocks), dim3(kExtLdsBlock), lds, s, sc, rays, n, out_t, out_mat, (uint32_t)lds);
     return hipGetLastError();
 }
-constexpr size_t kShadeLeafLds = 32768;      // stage the leaf records when they fit (256 leaves)
 hipError_t launch_shade(int mat, const DevScene& sc, const DevScene* scd, const RenderParams& rp, const PathState& in,
                         const HitBuf& hit, bool pt, const QView& qv, uint32_t n_upper,
                         const PathState& out, uint32_t* out_counts, uint32_t shard_cap, uint32_t depth, hipStream_t s) {
@@ -3990,29 +4003,44 @@ hipError_t launch_shade(int mat, const DevScene& sc, const DevScene* scd, const 
     pt = pt && mat == MAT_LAMBERTIAN;                  // the other queues hold HitRec in every launch
     const HitRec* hq = pt ? reinterpret_cast<const HitRec*>(hit.hp) : hit.h + (size_t)mat * hit.stride;
     const size_t leaf_lds = (size_t)sc.n_leaves * sizeof(LeafInfo);
-    const bool ll = leaf_lds <= kShadeLeafLds;
+    const ShadeInst si = shade_instance(mat, sc, rp, pt);
+    const bool ll = si.ll;
     // kTexPerlin / kTexImage kernels of every material carry the Perlin tables (metal albedo may be a noise texture)
     const bool pn = scene_tex_level(sc) >= kTexPerlin;
     const size_t lds = (ll ? leaf_lds : 0) + ((pn && mat != MAT_DIELECTRIC && sc.has_perlin) ? sizeof(PerlinLds) : 0);
-    hipLaunchKernelGGL(shade_kernel(mat, sc, rp, ll, pt), dim3(blocks), dim3(256), lds, s, scd, rp, in, hq, qv, out,
+    hipLaunchKernelGGL(shade_kernel(mat, si), dim3(blocks), dim3(256), lds, s, scd, rp, in, hq, qv, out,
                        out_counts, shard_cap, depth);
     return hipGetLastError();
+}
+// the time-0 tree rides in the tail kernel's LDS when it fits the caller's budget
+static bool finish_tree0_lds(const DevScene& sc, const size_t tree0_budget) {
+    const size_t tree = LdsTree(sc, false, false).record_bytes();
+    return sc.fbvh2 && tree0_budget > 0 && tree <= tree0_budget;
+}
+// the instance launch_finish takes (rt_launch.h FinishInst)
+FinishInst finish_instance(const DevScene& sc, const RenderParams& rp, const size_t tree0_budget) {
+    const int f = scene_features(sc).f;
+    const int tl = finish_tex_level(sc);
+    const bool ex = rp.exact_libm != 0;
+    if (f > 0) return FinishInst{f, tl == kTexImage ? kTexImage : kTexPerlin, light_mode(sc).v == 2 ? 2 : 1, false, ex};
+    // SOLO tail: plain-sphere world in one BVH, its time-0 tree in LDS, child refs within int16
+    const bool solo = finish_tree0_lds(sc, tree0_budget) && sc.bvh_solo && extend_lds_bytes(sc) > 0 &&
+                      sc.n_bvh2 < 32768 && sc.n_bleaf < 32768 && !finish_generic();
+    return FinishInst{0, tl, light_mode(sc).v, solo, ex};
 }
 hipError_t launch_finish(const DevScene& sc, const DevScene* scd, const RenderParams& rp, const PathState& st, const QView& in,
                          uint32_t n, unsigned long long* seg_count, size_t tree0_budget, uint32_t depth,
                          hipStream_t s) {
     uint32_t blocks = (n + 255u) / 256u;
     if (blocks > finish_blocks()) blocks = finish_blocks();   // persistent lanes refill from the path list
-    const size_t tree = LdsTree(sc, false, false).record_bytes();
-    const int tree0_lds = (sc.fbvh2 && tree0_budget > 0 && tree <= tree0_budget) ? 1 : 0;
-    // SOLO tail: plain-sphere world in one BVH, its time-0 tree in LDS, child refs within int16
-    const bool solo = tree0_lds && sc.bvh_solo && scene_features(sc).f == 0 && extend_lds_bytes(sc) > 0 &&
-                      sc.n_bvh2 < 32768 && sc.n_bleaf < 32768 && !finish_generic();
+    const int tree0_lds = finish_tree0_lds(sc, tree0_budget) ? 1 : 0;
+    const FinishInst fi = finish_instance(sc, rp, tree0_budget);
+    const bool solo = fi.solo;
     size_t lds = (lane_stack_lds(sc, solo ? sizeof(uint16_t) : sizeof(uint32_t)) + 15) / 16 * 16;
     if (tree0_lds) lds += LdsTree(sc, false, solo).record_bytes();
     // the Perlin tables ride at the end of the dynamic LDS, only where they are staged (TL >= kTexPerlin and tables given)
     if (finish_tex_level(sc) >= kTexPerlin && sc.has_perlin) lds += sizeof(PerlinLds);
-    hipLaunchKernelGGL(finish_kernel(sc, rp, solo), dim3(blocks), dim3(256), lds, s, scd, rp, st, in, n, seg_count,
+    hipLaunchKernelGGL(finish_kernel(fi), dim3(blocks), dim3(256), lds, s, scd, rp, st, in, n, seg_count,
                        tree0_lds, depth);
     return hipGetLastError();
 }

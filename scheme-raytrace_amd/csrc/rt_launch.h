@@ -31,6 +31,13 @@ hipError_t launch_shade(int mat, const DevScene& sc, const DevScene* scd, const 
 hipError_t launch_finish(const DevScene& sc, const DevScene* scd, const RenderParams& rp, const PathState& st,
                          const QView& in, uint32_t n, unsigned long long* seg_count, size_t tree0_budget,
                          uint32_t depth, hipStream_t s);
+// The template arguments of the k_shade<mat, TL, LS, LL, EX, PT> / k_finish<F, TL, LS, SOLO, EX> instance a
+// launch takes.  launch_shade and launch_finish form these records and pick their kernel from them alone, so
+// what rt_step_rays reports is what was launched.
+struct ShadeInst { int tl, ls; bool ll, ex, pt; };
+struct FinishInst { int f, tl, ls; bool solo, ex; };
+ShadeInst shade_instance(int mat, const DevScene& sc, const RenderParams& rp, bool pt);
+FinishInst finish_instance(const DevScene& sc, const RenderParams& rp, size_t tree0_budget);
 // bytes of LDS k_extend_lds needs for the scene's time-0 tree (0 = cannot run)
 size_t extend_lds_bytes(const DevScene& sc);
 // max_blocks: every block the kernel can keep on the device at once with `lds` bytes of dynamic LDS

@@ -677,6 +677,229 @@ int rt_light_probe(int scene, int n, const double* points, const double* dirs, u
     return 0;
 }
 
+/* RT_HAS_STEP_PROBE */
+int rt_step_rays(int scene, int n, const double* rays, const double* T_in, const uint32_t* ctr_in, const uint32_t* pix,
+                 uint64_t seed, uint32_t smp, int depth, int extend, int mode, int32_t* out_status, double* out_color,
+                 double* out_ray, double* out_T, uint32_t* out_ctr, double* out_t, int32_t* out_mat, int32_t* out_inst,
+                 uint32_t* out_survivors) {
+    LOCK_SCENE(s, scene);
+    if (!s->committed) return fail("scene not committed (rt_scene_commit)");
+    if (n < 0) return fail("rt_step_rays: record count must be >= 0");
+    if (!rays || !T_in || !ctr_in || !out_status || !out_color || !out_ray || !out_T || !out_ctr || !out_t || !out_mat ||
+        !out_inst || !out_survivors)
+        return fail("rt_step_rays: null pointer");
+    if (depth < 0 || depth > kMaxDepth) return fail("rt_step_rays: depth outside 0.." + std::to_string(kMaxDepth));
+    if (extend != RT_STEP_EXTEND_HBM && extend != RT_STEP_EXTEND_LDS)
+        return fail("rt_step_rays: unknown extend " + std::to_string(extend));
+    if (mode != RT_STEP_STEP && mode != RT_STEP_TAIL) return fail("rt_step_rays: unknown mode " + std::to_string(mode));
+    if (extend == RT_STEP_EXTEND_LDS && depth == 0)
+        return fail("rt_step_rays: the LDS extend serves depth >= 1 only (depth 0 is k_extend or k_camera)");
+    if (extend == RT_STEP_EXTEND_LDS && s->ext_lds == 0)
+        return fail("rt_step_rays: this scene's time-0 tree does not run from LDS (rt_scene_info.extend_lds_bytes is 0)");
+    if (curve_kernel_scene(s->dev))
+        return fail("rt_step_rays: this scene's renders take the persistent curve kernel, which the probe does not drive");
+    for (int k = 0; k < n; ++k) {
+        uint64_t bits;
+        if (depth == 0) {
+            for (int c = 0; c < 3; ++c)
+                if (!(T_in[3 * (size_t)k + c] == 1.0))
+                    return fail("rt_step_rays: a depth-0 path has throughput 1 (record " + std::to_string(k) + " has another)");
+        } else {
+            std::memcpy(&bits, &rays[7 * (size_t)k + 6], sizeof bits);
+            if (bits != 0)
+                return fail("rt_step_rays: a scattered ray has time +0.0 (record " + std::to_string(k) + " has another time)");
+        }
+    }
+    CTX_OF(c, s);
+    std::memset(out_inst, 0, 32 * sizeof(int32_t));
+    *out_survivors = 0;
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    {
+        uint32_t stale = 0;
+        HIPCHK(take_fault(&stale));
+        const char* e = std::getenv("RTAMD_REJECT_CAP");
+        HIPCHK(set_test_caps(e ? std::max(0, std::atoi(e)) : 4096, 0u));
+    }
+    // the layout of a render of n paths in one chunk (render_impl)
+    const size_t cap = (size_t)n;
+    const size_t gmax = std::min<size_t>(4096, (cap + 255) / 256 + kShards);
+    const size_t slack = 4 * 32 * gmax + 256;
+    const size_t shard_cap = (cap + kShards - 1) / kShards + slack;
+    const size_t scap = shard_cap * kShards;
+    constexpr int kCountsPerIter = 5 * kShards * kCntStride;
+    DevBuf b_a, b_b, b_hit, b_sb, b_cnt, b_ctl, b_pix;
+    HIPCHK(b_a.ensure(scap * kStateBytesA));
+    HIPCHK(b_b.ensure(scap * kStateBytesA));            // (either pool may be the depth's input: both carved alike)
+    HIPCHK(b_hit.ensure(scap * kHitBytesPerPath));
+    HIPCHK(b_sb.ensure(cap * 3 * sizeof(double)));
+    HIPCHK(b_cnt.ensure(2 * kCountsPerIter * sizeof(uint32_t)));     // row 0: the previous depth's, row 1: this one's
+    HIPCHK(b_ctl.ensure(4 * sizeof(unsigned long long)));
+    HIPCHK(b_pix.ensure(cap * sizeof(uint32_t)));
+    PathState A = carve_state(b_a.p, scap, true), B = carve_state(b_b.p, scap, true);
+    PathState* cur = (depth & 1) ? &B : &A;             // a chunk starts in pool A and swaps every depth
+    PathState* nxt = (depth & 1) ? &A : &B;
+
+    // host images of the input state
+    std::vector<uint32_t> h_pix(cap), slot_of(cap), h_prev(kCountsPerIter, 0u);
+    for (size_t k = 0; k < cap; ++k) h_pix[k] = pix ? pix[k] : (uint32_t)k;
+    std::vector<RayRec> h_ray(scap);
+    std::vector<PathRec> h_path(scap);
+    std::vector<double> h_tm(scap, 0.0);
+    std::vector<uint32_t> h_rng0(scap, 0u);
+    std::memset(h_ray.data(), 0, scap * sizeof(RayRec));
+    std::memset(h_path.data(), 0, scap * sizeof(PathRec));
+    for (size_t k = 0; k < cap; ++k) {
+        size_t slot = k;
+        if (depth > 0) {
+            const size_t shard = (k / 256) % kShards;
+            slot = shard * shard_cap + h_prev[(4 * kShards + shard) * kCntStride]++;
+        }
+        slot_of[k] = (uint32_t)slot;
+        const double* r = rays + 7 * k;
+        RayRec R{};
+        R.ox = r[0]; R.oy = r[1]; R.oz = r[2]; R.dx = r[3]; R.dy = r[4]; R.dz = r[5];
+        h_ray[slot] = R;
+        if (depth == 0) {
+            h_tm[slot] = r[6];
+            h_rng0[slot] = ctr_in[k];
+        } else {
+            PathRec P{};
+            P.tr = T_in[3 * k]; P.tg = T_in[3 * k + 1]; P.tb = T_in[3 * k + 2];
+            P.wid = (uint32_t)k; P.rng = ctr_in[k];
+            h_path[slot] = P;
+        }
+    }
+    std::vector<uint32_t> key_of(scap, 0xFFFFFFFFu);      // input slot -> record
+    for (size_t k = 0; k < cap; ++k) key_of[slot_of[k]] = (uint32_t)k;
+    std::vector<uint64_t> h_sb(cap * 3, (uint64_t)RT_STEP_SENTINEL);
+
+    HIPCHK(hipMemcpyAsync(cur->ray, h_ray.data(), scap * sizeof(RayRec), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(cur->path, h_path.data(), scap * sizeof(PathRec), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(cur->tm, h_tm.data(), scap * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(cur->rng0, h_rng0.data(), scap * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(nxt->ray, 0, scap * sizeof(RayRec), st));
+    HIPCHK(hipMemsetAsync(nxt->path, 0xFF, scap * sizeof(PathRec), st));
+    HIPCHK(hipMemcpyAsync(b_pix.p, h_pix.data(), cap * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b_sb.p, h_sb.data(), cap * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(b_cnt.p, 0, 2 * kCountsPerIter * sizeof(uint32_t), st));
+    HIPCHK(hipMemcpyAsync(b_cnt.p, h_prev.data(), kCountsPerIter * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(b_hit.p, 0, scap * kHitBytesPerPath, st));
+    HIPCHK(hipMemsetAsync(b_ctl.p, 0, 4 * sizeof(unsigned long long), st));
+
+    RenderParams rp{};
+    rp.nx = (uint32_t)n; rp.ny = 1u; rp.npix = (uint32_t)n;
+    rp.inx = 1.0 / (double)n; rp.iny = 1.0;
+    rp.spp0 = smp; rp.k0 = (uint32_t)seed; rp.k1 = (uint32_t)(seed >> 32);
+    rp.pixlist = b_pix.as<const uint32_t>();
+    rp.sb = b_sb.as<double>();
+    rp.B = (uint32_t)n;
+    rp.compact = 0u;
+    rp.exact_libm = scene_exact_libm(*c, *s) ? 1u : 0u;
+    // the survivor view of the previous depth (raygen's output is contiguous)
+    const QView view = depth == 0 ? QView{nullptr, (uint32_t)scap}
+                                  : QView{b_cnt.as<uint32_t>() + 4 * kShards * kCntStride, (uint32_t)shard_cap};
+    uint32_t* cnt = b_cnt.as<uint32_t>() + kCountsPerIter;
+    unsigned long long* ctl = b_ctl.as<unsigned long long>();
+    const HitBuf hit{b_hit.as<HitRec>() + scap, (uint32_t)scap, b_hit.as<HitPt>()};
+    const size_t tree0_budget = s->ext_lds ? (size_t)32 << 10 : 0;
+    const bool ext_lds = extend == RT_STEP_EXTEND_LDS;
+    const bool pt = s->point_hits && !point_hits_off() && ext_lds;
+
+    if (mode == RT_STEP_TAIL) {
+        const FinishInst fi = finish_instance(s->dev, rp, tree0_budget);
+        const int32_t row[6] = {1, fi.f, fi.tl, fi.ls, fi.solo ? 1 : 0, fi.ex ? 1 : 0};
+        std::memcpy(out_inst, row, sizeof row);
+        HIPCHK(launch_finish(s->dev, s->d_dev.as<const DevScene>(), rp, *cur, view, (uint32_t)n, ctl, tree0_budget,
+                             (uint32_t)depth, st));
+    } else {
+        if (ext_lds)
+            HIPCHK(launch_extend_lds(s->dev, rp, *cur, view, (uint32_t)n, hit, pt, (uint32_t)shard_cap, cnt,
+                                     s->ext_lds_blocks, ctl + 2, st));
+        else
+            HIPCHK(launch_extend(s->dev, s->d_dev.as<const DevScene>(), rp, *cur, view, (uint32_t)n, hit,
+                                 (uint32_t)shard_cap, cnt, depth == 0, reinterpret_cast<unsigned int*>(ctl + 1), nullptr, st));
+        uint32_t* surv = cnt + 4 * kShards * kCntStride;
+        for (int mt = 0; mt < 4; ++mt) {
+            if (!(s->dev.mat_mask & (1 << mt))) continue;
+            const ShadeInst si = shade_instance(mt, s->dev, rp, pt && mt == MAT_LAMBERTIAN);
+            const int32_t row[6] = {1, si.tl, si.ls, si.ll ? 1 : 0, si.ex ? 1 : 0, si.pt ? 1 : 0};
+            std::memcpy(out_inst + 8 * mt, row, sizeof row);
+            const QView qv{cnt + mt * kShards * kCntStride, (uint32_t)shard_cap};
+            HIPCHK(launch_shade(mt, s->dev, s->d_dev.as<const DevScene>(), rp, *cur, hit, pt, qv, (uint32_t)n, *nxt, surv,
+                                (uint32_t)shard_cap, (uint32_t)depth, st));
+        }
+    }
+    // read everything back
+    std::vector<uint32_t> h_cnt(kCountsPerIter);
+    std::vector<HitRec> h_hit(5 * scap);
+    std::vector<LeafInfo> h_leaves((size_t)std::max(0, s->dev.n_leaves));
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), cnt, kCountsPerIter * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_sb.data(), b_sb.p, cap * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (mode == RT_STEP_STEP) {
+        HIPCHK(hipMemcpyAsync(h_ray.data(), nxt->ray, scap * sizeof(RayRec), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_path.data(), nxt->path, scap * sizeof(PathRec), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_hit.data(), b_hit.p, scap * kHitBytesPerPath, hipMemcpyDeviceToHost, st));
+        if (!h_leaves.empty())
+            HIPCHK(hipMemcpyAsync(h_leaves.data(), s->dev.leaves, h_leaves.size() * sizeof(LeafInfo), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    {
+        uint32_t f = 0;
+        HIPCHK(take_fault(&f));
+        if (f) return fail(fault_text(f));
+        unsigned long long h_ctl[4] = {0, 0, 0, 0};
+        HIPCHK(hipMemcpy(h_ctl, b_ctl.p, sizeof h_ctl, hipMemcpyDeviceToHost));
+        if (h_ctl[2]) return fail("internal: a persistent kernel's LDS allocation was too small (flags " +
+                                  std::to_string(h_ctl[2]) + ")");
+    }
+    for (size_t k = 0; k < cap; ++k) {
+        bool wrote = false;
+        for (int c3 = 0; c3 < 3; ++c3) wrote = wrote || h_sb[3 * k + c3] != (uint64_t)RT_STEP_SENTINEL;
+        out_status[k] = wrote ? RT_STEP_WROTE : 0;
+        std::memcpy(out_color + 3 * k, &h_sb[3 * k], 3 * sizeof(double));
+    }
+    if (mode == RT_STEP_TAIL) return 0;
+    for (size_t k = 0; k < cap; ++k) { out_t[k] = 0.0; out_mat[k] = -1; }
+    uint32_t total = 0;
+    for (int x = 0; x < kShards; ++x) {
+        const uint32_t cx = h_cnt[(4 * kShards + x) * kCntStride];
+        if (cx > shard_cap) return fail("internal: shard overflow");
+        total += cx;
+        for (uint32_t j = 0; j < cx; ++j) {
+            const size_t slot = (size_t)x * shard_cap + j;
+            const PathRec& P = h_path[slot];
+            if (P.wid >= (uint32_t)n) return fail("rt_step_rays: a survivor carries work id " + std::to_string(P.wid));
+            const size_t k = P.wid;
+            if ((out_status[k] & 255) < 255) ++out_status[k];
+            const RayRec& R = h_ray[slot];
+            const double ray6[6] = {R.ox, R.oy, R.oz, R.dx, R.dy, R.dz};
+            std::memcpy(out_ray + 6 * k, ray6, sizeof ray6);
+            out_T[3 * k] = P.tr; out_T[3 * k + 1] = P.tg; out_T[3 * k + 2] = P.tb;
+            out_ctr[k] = P.rng;
+        }
+    }
+    *out_survivors = total;
+    // the hit queues: HitBuf's layout (queue m of HitRec at stride (1 + m); the point records from the start)
+    const HitPt* h_pt = reinterpret_cast<const HitPt*>(h_hit.data());
+    for (int mt = 0; mt < 4; ++mt)
+        for (int x = 0; x < kShards; ++x) {
+            const uint32_t cx = std::min<uint32_t>(h_cnt[(mt * kShards + x) * kCntStride], (uint32_t)shard_cap);
+            for (uint32_t j = 0; j < cx; ++j) {
+                const size_t q = (size_t)x * shard_cap + j;
+                int32_t leaf; uint32_t slot; double t;
+                if (pt && mt == MAT_LAMBERTIAN) { leaf = h_pt[q].leaf; slot = h_pt[q].slot; t = std::nan(""); }
+                else { const HitRec& H = h_hit[(size_t)(1 + mt) * scap + q]; leaf = H.leaf; slot = H.slot; t = H.t; }
+                if (slot >= scap || key_of[slot] == 0xFFFFFFFFu || leaf < 0 || leaf >= s->dev.n_leaves)
+                    return fail("rt_step_rays: a hit queue holds a record of no input path");
+                out_t[key_of[slot]] = t;
+                out_mat[key_of[slot]] = h_leaves[leaf].mat;
+            }
+        }
+    return 0;
+}
+
 int rt_curve_depth_probe(int ctx, int n, const double* cps, const double* eps8, int32_t* out_depth) {
     LOCK_CTX(c, ctx);
     if (n < 0) return fail("curve count must be >= 0");

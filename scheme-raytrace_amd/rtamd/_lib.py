@@ -170,6 +170,10 @@ _SIGNATURES = {
                         ctypes.POINTER(ctypes.c_int64)],
     "rt_resolve_u8_device": [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                              ctypes.c_void_p, ctypes.c_void_p],
+    "rt_step_rays": [ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_uint32),    # RT_HAS_STEP_PROBE
+                     ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
+                     ctypes.c_int, _c_i32_p, _c_double_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_uint32),
+                     _c_double_p, _c_i32_p, _c_i32_p, ctypes.POINTER(ctypes.c_uint32)],
     "rt_curve_depth_probe": [ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p, _c_i32_p],
     "rt_comm_unique_id": [ctypes.POINTER(ctypes.c_uint8)],
     "rt_comm_create": [ctypes.c_int, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int, ctypes.c_int, _c_int_p],

@@ -366,6 +366,62 @@ def light_probe(scene, points, seed, dirs=None, ctx=None):
     return out_dir, out_pdf, out_pdf_dirs, draws
 
 
+#: rt_step_rays' extends, modes and status bit (include/rt.h)
+STEP_EXTEND_HBM, STEP_EXTEND_LDS = 0, 1
+STEP_STEP, STEP_TAIL = 0, 1
+STEP_WROTE = 256
+STEP_SENTINEL = 0x7FF8DEAD5CA77E12
+
+
+class StepResult:
+    """rt_step_rays' outputs.  status (n,) int32: survivor entries of the record | STEP_WROTE; color (n, 3) the
+    record's sample slot; ray (n, 6), T (n, 3), ctr (n,) the survivor; t (n,), mat (n,) the queued hit (-1: none);
+    survivors: the device's survivor count; shade: {material type: (TL, LS, LL, EX, PT)} of the k_shade
+    instances launched (STEP); finish: (F, TL, LS, SOLO, EX) of the k_finish instance (TAIL), else None."""
+    __slots__ = ("status", "color", "ray", "T", "ctr", "t", "mat", "survivors", "shade", "finish")
+
+    def wrote(self):
+        return (self.status & STEP_WROTE) != 0
+
+    def entries(self):
+        return self.status & 255
+
+
+def step_rays(scene, rays, T_in=None, ctr_in=None, pix=None, seed=0, smp=0, depth=0, extend=STEP_EXTEND_HBM,
+              mode=STEP_STEP, ctx=None):
+    """rt_step_rays: one wavefront iteration (extend + every material's shade, or the tail kernel) on the
+    caller's path states.  rays (n, 7) float64 (origin, direction, time); T_in (n, 3), default 1; ctr_in (n,),
+    default 0; pix (n,) or None (pixel key k).  Returns a StepResult."""
+    h = upload(scene, ctx)
+    dp, ip, up = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32)
+    r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 7)
+    n = r.shape[0]
+    T = np.ones((n, 3)) if T_in is None else np.ascontiguousarray(T_in, dtype=np.float64).reshape(-1, 3)
+    c = np.zeros(n, dtype=np.uint32) if ctr_in is None else np.ascontiguousarray(ctr_in, dtype=np.uint32).reshape(-1)
+    p = None if pix is None else np.ascontiguousarray(pix, dtype=np.uint32).reshape(-1)
+    if T.shape[0] != n or c.shape[0] != n or (p is not None and p.shape[0] != n):
+        raise ValueError("one throughput, counter and pixel key per ray")
+    res = StepResult()
+    res.status = np.zeros(n, dtype=np.int32)
+    res.color, res.ray, res.T = np.zeros((n, 3)), np.zeros((n, 6)), np.zeros((n, 3))
+    res.ctr, res.t, res.mat = np.zeros(n, dtype=np.uint32), np.zeros(n), np.full(n, -1, dtype=np.int32)
+    inst = np.zeros(32, dtype=np.int32)
+    surv = ctypes.c_uint32(0)
+    call("rt_step_rays", h, n, r.ctypes.data_as(dp), T.ctypes.data_as(dp), c.ctypes.data_as(up),
+         p.ctypes.data_as(up) if p is not None else None, _u64(seed), ctypes.c_uint32(int(smp)), int(depth), int(extend),
+         int(mode), res.status.ctypes.data_as(ip), res.color.ctypes.data_as(dp), res.ray.ctypes.data_as(dp),
+         res.T.ctypes.data_as(dp), res.ctr.ctypes.data_as(up), res.t.ctypes.data_as(dp), res.mat.ctypes.data_as(ip),
+         inst.ctypes.data_as(ip), ctypes.byref(surv))
+    res.survivors = int(surv.value)
+    res.shade, res.finish = {}, None
+    if n and mode == STEP_TAIL:
+        res.finish = (int(inst[1]), int(inst[2]), int(inst[3]), bool(inst[4]), bool(inst[5]))
+    elif n:
+        res.shade = {m: (int(inst[8 * m + 1]), int(inst[8 * m + 2]), bool(inst[8 * m + 3]), bool(inst[8 * m + 4]),
+                         bool(inst[8 * m + 5])) for m in range(4) if inst[8 * m]}
+    return res
+
+
 def resolve_u8(accum, nx, ny, sample_count):
     """rt_resolve_u8 (main.scm:481-491) on the host."""
     a = np.ascontiguousarray(accum, dtype=np.float64).ravel()

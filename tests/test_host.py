@@ -33,6 +33,17 @@ def test_library_exports_every_header_symbol():
     assert sorted(_lib.EXPORTED) == decl            # the ctypes binding covers the whole ABI
 
 
+def test_step_probe_checks_its_scene_before_any_device_work():
+    """rt_step_rays (RT_HAS_STEP_PROBE) refuses a bad handle on the host, with a message."""
+    L = _lib.lib()
+    d = (ctypes.c_double * 8)()
+    i = (ctypes.c_int32 * 32)()
+    u = (ctypes.c_uint32 * 4)()
+    assert "RT_HAS_STEP_PROBE 1" in open(os.path.join(ROOT, "include", "rt.h")).read()
+    assert L.rt_step_rays(-5, 1, d, d, u, None, 1, 0, 0, 0, 0, i, d, d, d, u, d, i, i, u) != 0
+    assert b"invalid scene handle" in L.rt_last_error()
+
+
 def test_library_loads_and_reports_errors_without_gpu():
     L = _lib.lib()
     assert L.rt_abi_version() == 7
