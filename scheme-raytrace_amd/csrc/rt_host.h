@@ -4,7 +4,8 @@
 //   rt_scene.cpp     contexts, options, the scene builder, statistics
 //   rt_build.cpp     the host scene of a commit: flattening, BVH builds, records (build_scene; no HIP)
 //   rt_commit.cpp    its upload and the device-dependent sizing (commit_scene)
-//   rt_render.cpp    the render scheduler (render_impl) and the render / probe / resolve entry points
+//   rt_render.cpp    the render scheduler (render_impl; its arithmetic: rt_plan.h) and the render / resolve entry points
+//   rt_probe.cpp     the probe entry points (rt_hit_rays*, rt_light_probe, rt_step_rays, rt_curve_depth_probe)
 //   rt_gather.cpp    the frame-end gather (RCCL and in-process)
 //   rt_adaptive.cpp  adaptive sampling
 //   rt_features.cpp  first-hit feature buffers
@@ -23,6 +24,7 @@
 #include "../../include/rt.h"
 #include "rt_device.h"
 #include "rt_model.h"
+#include "rt_plan.h"
 
 namespace rtamd {
 
@@ -61,9 +63,8 @@ struct DevBuf {
 // long, narrow tail of one chunk (its last few paths bouncing to depth 100)
 // overlaps the wide first iterations of the next one instead of leaving the
 // chip mostly idle.  Accumulation stays in chunk (= sample) order.
-constexpr int kLanes = 4;                  // most lanes a render may use (RT_OPT_LANES)
 struct Lane {
-    DevBuf st_a, st_b, hit, sb, counts, seg_tail;
+    DevBuf st_a, st_b, hit, sb, counts, seg_tail;      // (rt_plan.h PoolLayout; seg_tail: the LaneCtl words)
     uint32_t* h_counts = nullptr;              // pinned survivor counts, one row per iteration
     hipStream_t stream = nullptr;
     hipEvent_t ev_cnt = nullptr;               // the last iteration's survivor counts are on the host
@@ -256,5 +257,45 @@ int render_impl(Scene* s, int nx, int ny, const PixSet& px, int spp_begin, int s
 // the selection differs from the cached one); and rt_last_error's text for a device fault word
 int pixset_of(Scene* s, int nx, int ny, const PixSel& ps, bool compact, PixSet* out);
 std::string fault_text(uint32_t f);
+
+// rt_render.cpp: what a scene's renders decide from the context and the environment, for the probes too.
+// the libm mode a scene's renders (and rt_light_probe) take under the context's RT_OPT_EXACT_LIBM
+bool scene_exact_libm(const Context& c, const Scene& s);
+// The persistent curve kernels serve scenes whose world BVH holds every curve (launch_extend)
+bool curve_kernel_scene(const DevScene& d);
+// RTAMD_NO_POINT_HITS (A/B, tests; read per render): every hit queue keeps HitRec
+bool point_hits_off();
+
+// One step of a chunk as renders and rt_step_rays enqueue it.  The closest-hit launch of a wavefront
+// iteration: k_camera (raygen + the first hit, depth 0), k_extend_lds (depth >= 1, the time-0 tree in LDS) or
+// k_extend / the persistent curve kernel.
+enum class ExtendPath { CAMERA, LDS, HBM };
+// point records are what the SOLO LDS kernels write, so a render can mix the two formats across depths:
+// one of those kernels switched off, or a chunk whose depth 0 is k_raygen + k_extend
+inline bool point_records(bool point_hits, ExtendPath path) {
+    return point_hits && (path == ExtendPath::CAMERA || path == ExtendPath::LDS);
+}
+// LDS bytes the tail kernel's time-0 tree may take
+inline size_t tree0_budget(const Scene& s) { return s.ext_lds ? (size_t)32 << 10 : 0; }
+struct StepArgs {
+    const RenderParams& rp;
+    const PathState& cur;                      // the n live paths, seen through `in` (the previous depth's
+    const PathState& nxt;                      // survivors; contiguous at depth 0), and where survivors go
+    QView in;
+    uint32_t n;
+    int depth;
+    const PoolLayout& lay;
+    void* hit;                                 // the hit queues' buffer (lay.hit_bytes)
+    uint32_t* counts;                          // this depth's counter row (kCountsPerIter words, zero)
+    unsigned long long* ctl;                   // the LaneCtl words
+    int lane;                                  // the render lane's index: its region of the curve walk's buffers
+    bool point_hits;                           // the scene's, unless switched off (point_hits_off)
+    hipStream_t stream;
+};
+// extend + the shade of every material the scene has; may_fuse: a curve-kernel scene's depth >= 1 may take
+// the fused curve extend, which shades its hits itself; ev: null, or three events recorded around the two
+int enqueue_iteration(const Scene& s, const StepArgs& a, ExtendPath path, bool may_fuse, const hipEvent_t* ev);
+// the tail kernel, which finishes the n paths; ev: null, or two events recorded around it
+int enqueue_tail(const Scene& s, const StepArgs& a, const std::pair<hipEvent_t, hipEvent_t>* ev);
 
 }  // namespace rtamd
