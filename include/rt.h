@@ -450,11 +450,14 @@ int rt_hit_rays_stream(int scene, const double* rays, int n, uint64_t seed, doub
  * mode the scene's renders take (RT_OPT_EXACT_LIBM).  The sample buffer is pre-filled with the NaN pattern
  * 0x7FF8DEAD5CA77E12 in every double (RT_STEP_SENTINEL): a slot that still holds it was not written.
  *
- * extend: RT_STEP_EXTEND_HBM = launch_extend (k_extend<F>, HitRec queues, depth0 = (depth == 0));
+ * extend: RT_STEP_EXTEND_HBM = launch_extend (HitRec queues, depth0 = (depth == 0)): k_extend<F>, or, in
+ * scenes whose renders take the persistent curve kernel (every curve in the world BVH, no media, no Klein
+ * set; RT_HAS_CURVE_STEP), k_extend_curves<0> exactly as a render launches it: the grid launch_extend sizes
+ * (RTAMD_CURVE_BLOCKS caps it, 0 selects the per-ray k_extend), render lane 0's regions of the walk's stack
+ * overflow area and rings, the claim word among the control words, appends that spill between shards.
  * RT_STEP_EXTEND_LDS = launch_extend_lds (depth >= 1 and rt_scene_info.extend_lds_bytes > 0 only), which
- * queues lambertian hits as point records exactly when a render's would (rt_scene_point_hits).  Scenes whose
- * renders take the persistent curve kernel (every curve in the world BVH, no media, no Klein set) are
- * refused.  Scenes with media are allowed: the hit test draws, and the shade continues from its counter.
+ * queues lambertian hits as point records exactly when a render's would (rt_scene_point_hits).
+ * Scenes with media are allowed: the hit test draws, and the shade continues from its counter.
  *
  * mode RT_STEP_STEP: after the extend, launch_shade for every material type of the scene.  Outputs per
  * record k: out_status[k] = (times wid k appears among the survivors) | RT_STEP_WROTE if its sample slot no
@@ -463,18 +466,28 @@ int rt_hit_rays_stream(int scene, const double* rays, int n, uint64_t seed, doub
  * id, out_mat -1 (t 0) for a record in no hit queue, t NaN for a point record (it carries no t).
  * *out_survivors = the sum of the device's survivor counters.  out_inst[8m..8m+5] for material type m =
  * {launched, TL, LS, LL, EX, PT} of the k_shade instance launch_shade took (all 0 when the scene has no such
- * material).
+ * material).  out_inst[7] = the extend launch_extend took (RT_STEP_EXTEND_HBM; RT_HAS_CURVE_STEP): 0 k_extend<F>,
+ * 1 k_extend_curves<0>, 2 / 3 k_extend_curves<FUSE> with the device / the exact libm (RT_STEP_FUSED only).
  * mode RT_STEP_TAIL: launch_finish on the same state at `depth` instead of extend + shade; out_color /
  * out_status as above (no survivors), out_inst[0..5] = {1, F, TL, LS, SOLO, EX} of the k_finish instance;
- * the other outputs are left alone.
- * The instance tuples come from the selection functions launch_shade / launch_finish themselves call.
+ * the other outputs are left alone.  Curve-kernel scenes are taken like any other.
+ * mode RT_STEP_FUSED (RT_HAS_CURVE_STEP): the iteration as a render enqueues it at depth >= 1 in a scene whose
+ * depth >= 1 launches take the fused curve extend: k_extend_curves<FUSE> runs every record to its end and
+ * shades the hits itself.  out_color / out_status as for RT_STEP_TAIL (no survivors), out_inst[7] = 2 or 3,
+ * *out_survivors = the continuation segments the launch counted (every closest-hit query past each record's
+ * first); the other outputs are left alone.
+ * The instance tuples come from the selection functions launch_shade / launch_finish / launch_extend
+ * themselves call.
  *
  * Refused before any device work: null pointers (pix excepted), n < 0, depth outside 0..100, an unknown
- * extend or mode, an uncommitted scene, RT_STEP_EXTEND_LDS at depth 0 or in a scene without that kernel.
+ * extend or mode, an uncommitted scene, RT_STEP_EXTEND_LDS at depth 0 or in a scene without that kernel,
+ * RT_STEP_FUSED at depth 0, with RT_STEP_EXTEND_LDS, or where a render would not fuse (the error names why: not
+ * a curve-kernel scene, Perlin or image textures, a sampled light, RTAMD_CURVE_FUSE=0, RTAMD_CURVE_BLOCKS=0).
  * n = 0 returns at once with *out_survivors = 0 and out_inst cleared. */
 #define RT_HAS_STEP_PROBE 1
 enum { RT_STEP_EXTEND_HBM = 0, RT_STEP_EXTEND_LDS = 1 };
-enum { RT_STEP_STEP = 0, RT_STEP_TAIL = 1 };
+#define RT_HAS_CURVE_STEP 1
+enum { RT_STEP_STEP = 0, RT_STEP_TAIL = 1, RT_STEP_FUSED = 2 };
 enum { RT_STEP_WROTE = 256 };
 #define RT_STEP_SENTINEL 0x7FF8DEAD5CA77E12ull
 int rt_step_rays(int scene, int n, const double* rays, const double* T_in, const uint32_t* ctr_in,

@@ -265,6 +265,8 @@ bool scene_exact_libm(const Context& c, const Scene& s);
 bool curve_kernel_scene(const DevScene& d);
 // RTAMD_NO_POINT_HITS (A/B, tests; read per render): every hit queue keeps HitRec
 bool point_hits_off();
+// null when a depth >= 1 launch of n rays takes the fused curve extend (k_extend_curves<FUSE>), else why not
+const char* curve_fuse_refusal(const DevScene& d, uint32_t n);
 
 // One step of a chunk as renders and rt_step_rays enqueue it.  The closest-hit launch of a wavefront
 // iteration: k_camera (raygen + the first hit, depth 0), k_extend_lds (depth >= 1, the time-0 tree in LDS) or
@@ -293,8 +295,10 @@ struct StepArgs {
     hipStream_t stream;
 };
 // extend + the shade of every material the scene has; may_fuse: a curve-kernel scene's depth >= 1 may take
-// the fused curve extend, which shades its hits itself; ev: null, or three events recorded around the two
-int enqueue_iteration(const Scene& s, const StepArgs& a, ExtendPath path, bool may_fuse, const hipEvent_t* ev);
+// the fused curve extend, which shades its hits itself; ev: null, or three events recorded around the two;
+// extend_inst: null, or where launch_extend leaves the ExtendInst it took (ExtendPath::HBM only)
+int enqueue_iteration(const Scene& s, const StepArgs& a, ExtendPath path, bool may_fuse, const hipEvent_t* ev,
+                      int* extend_inst = nullptr);
 // the tail kernel, which finishes the n paths; ev: null, or two events recorded around it
 int enqueue_tail(const Scene& s, const StepArgs& a, const std::pair<hipEvent_t, hipEvent_t>* ev);
 

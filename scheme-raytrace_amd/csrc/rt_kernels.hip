@@ -3734,9 +3734,17 @@ using FeaturesKernel = void (*)(DevScene, RenderParams, uint32_t, double*);
 static ExtendKernel extend_kernel(const DevScene& sc) {
     return dispatch([](auto F) -> ExtendKernel { return k_extend<F()>; }, scene_features(sc));
 }
-// FUSE: 0 one depth, 1 every depth from fuse->depth on with the device libm, 2 with the exact libm
-static CurveKernel curve_kernel(const RenderParams& rp, const CurveFuse* fuse) {
-    return dispatch([](auto FUSE) -> CurveKernel { return k_extend_curves<FUSE()>; }, UpTo<2>{!fuse ? 0 : rp.exact_libm ? 2 : 1});
+// The persistent curve kernel: every curve in the world BVH (its groups outside the BVH are spheres and
+// rects only: group_closest<0>, so the per-lane curve walk is not compiled into it), a claim word, and
+// RTAMD_CURVE_BLOCKS not 0.  FUSE: 0 one depth, 1 every depth from fuse->depth on with the device libm, 2 with
+// the exact libm
+ExtendInst extend_instance(const DevScene& sc, const RenderParams& rp, const bool claim, const bool fuse) {
+    if (!(scene_features(sc).f == kFeatCurves && sc.bvh_has_bez && sc.bez_groups == 0 && claim && curve_blocks() > 0))
+        return EXTEND_PER_RAY;
+    return !fuse ? EXTEND_CURVES : rp.exact_libm ? EXTEND_CURVES_FUSED_EXACT : EXTEND_CURVES_FUSED;
+}
+static CurveKernel curve_kernel(const ExtendInst inst) {          // inst: one of the curve instances
+    return dispatch([](auto FUSE) -> CurveKernel { return k_extend_curves<FUSE()>; }, UpTo<2>{(int)inst - (int)EXTEND_CURVES});
 }
 // SOLO: the world is one BVH group; pt (SOLO only): lambertian hits as point records
 static ExtendLdsKernel extend_lds_kernel(const DevScene& sc, const bool pt) {
@@ -3852,15 +3860,16 @@ static hipError_t curve_occupancy(const CurveKernel k, const size_t lds, uint32_
 }
 hipError_t launch_extend(const DevScene& sc, const DevScene*, const RenderParams& rp, const PathState& st, const QView& in,
                          uint32_t n, const HitBuf& hit, uint32_t shard_cap,
-                         uint32_t* counts, bool depth0, unsigned int* claim, const CurveFuse* fuse, hipStream_t s) {
+                         uint32_t* counts, bool depth0, unsigned int* claim, const CurveFuse* fuse, hipStream_t s,
+                         int* inst_out) {
     const uint32_t blocks = (n + 255u) / 256u;
-    // the persistent curve kernel: every curve in the world BVH (its groups outside the BVH are spheres and
-    // rects only: group_closest<0>, so the per-lane curve walk is not compiled into it)
-    if (scene_features(sc).f == kFeatCurves && sc.bvh_has_bez && sc.bez_groups == 0 && claim && curve_blocks() > 0) {
+    const ExtendInst inst = extend_instance(sc, rp, claim != nullptr, fuse != nullptr);
+    if (inst_out) *inst_out = (int)inst;
+    if (inst != EXTEND_PER_RAY) {
         // resident blocks only: later blocks would find the rays claimed.  The BVH4 walk's LDS stack column
         // holds lds4 entries per lane (the rest in the overflow area).  Occupancy per (device, LDS bytes)
         const size_t clds = (size_t)256 * (size_t)(sc.lds4 > 0 ? sc.lds4 : 1) * sizeof(uint32_t);
-        const CurveKernel k = curve_kernel(rp, fuse);
+        const CurveKernel k = curve_kernel(inst);
         uint32_t occ_blocks = 0;
         if (const hipError_t e = curve_occupancy(k, clds, &occ_blocks)) return e;
         uint32_t pb = blocks < occ_blocks ? blocks : occ_blocks;

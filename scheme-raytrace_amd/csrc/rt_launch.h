@@ -16,10 +16,16 @@ namespace rtamd {
 hipError_t launch_raygen(const DevScene& sc, const RenderParams& rp, const PathState& st, hipStream_t s);
 // in: the survivor queue view of the previous depth (contiguous for raygen's output); counts: this
 // iteration's [material][shard] hit counters; claim: the persistent curve kernel's next-ray counter
-// (null: per-ray k_extend only); fuse: non-null runs every depth >= 1 in this launch (curve-kernel scenes)
+// (null: per-ray k_extend only); fuse: non-null runs every depth >= 1 in this launch (curve-kernel scenes);
+// inst: null, or where the launch leaves the ExtendInst it took
 hipError_t launch_extend(const DevScene& sc, const DevScene* scd, const RenderParams& rp, const PathState& st,
                          const QView& in, uint32_t n, const HitBuf& hit, uint32_t shard_cap, uint32_t* counts,
-                         bool depth0, unsigned int* claim, const CurveFuse* fuse, hipStream_t s);
+                         bool depth0, unsigned int* claim, const CurveFuse* fuse, hipStream_t s, int* inst = nullptr);
+// The extend launch_extend takes: k_extend<F>, k_extend_curves<0>, or k_extend_curves<FUSE> with the device (1)
+// or the exact (2) libm.  launch_extend forms this value and picks its kernel from it alone, so what
+// rt_step_rays reports is what was launched.
+enum ExtendInst { EXTEND_PER_RAY = 0, EXTEND_CURVES = 1, EXTEND_CURVES_FUSED = 2, EXTEND_CURVES_FUSED_EXACT = 3 };
+ExtendInst extend_instance(const DevScene& sc, const RenderParams& rp, bool claim, bool fuse);
 // mat: the material whose hit queue (qv, at most n_upper hits) is shaded; out / out_counts: the next
 // depth's path state and its per-shard survivor counters; pt: the launch that filled the queues wrote the
 // lambertian one as point records (launch_camera / launch_extend_lds with pt)

@@ -255,13 +255,18 @@ int rt_step_rays(int scene, int n, const double* rays, const double* T_in, const
     if (depth < 0 || depth > kMaxDepth) return fail("rt_step_rays: depth outside 0.." + std::to_string(kMaxDepth));
     if (extend != RT_STEP_EXTEND_HBM && extend != RT_STEP_EXTEND_LDS)
         return fail("rt_step_rays: unknown extend " + std::to_string(extend));
-    if (mode != RT_STEP_STEP && mode != RT_STEP_TAIL) return fail("rt_step_rays: unknown mode " + std::to_string(mode));
+    if (mode != RT_STEP_STEP && mode != RT_STEP_TAIL && mode != RT_STEP_FUSED)
+        return fail("rt_step_rays: unknown mode " + std::to_string(mode));
     if (extend == RT_STEP_EXTEND_LDS && depth == 0)
         return fail("rt_step_rays: the LDS extend serves depth >= 1 only (depth 0 is k_extend or k_camera)");
     if (extend == RT_STEP_EXTEND_LDS && s->ext_lds == 0)
         return fail("rt_step_rays: this scene's time-0 tree does not run from LDS (rt_scene_info.extend_lds_bytes is 0)");
-    if (curve_kernel_scene(s->dev))
-        return fail("rt_step_rays: this scene's renders take the persistent curve kernel, which the probe does not drive");
+    if (mode == RT_STEP_FUSED) {
+        if (depth == 0) return fail("rt_step_rays: the fused curve extend serves depth >= 1 only (depth 0 is one launch of its own)");
+        if (extend != RT_STEP_EXTEND_HBM) return fail("rt_step_rays: the fused curve extend is an RT_STEP_EXTEND_HBM launch");
+        if (const char* why = curve_fuse_refusal(s->dev, (uint32_t)n))
+            return fail(std::string("rt_step_rays: a render of this scene would not take the fused curve extend: ") + why);
+    }
     for (int k = 0; k < n; ++k) {
         uint64_t bits;
         if (depth == 0) {
@@ -335,7 +340,12 @@ int rt_step_rays(int scene, int n, const double* rays, const double* T_in, const
     const bool point_hits = s->point_hits && !point_hits_off(), pt = point_records(point_hits, path);
     const StepArgs a{rp, cur, nxt, view, (uint32_t)n, depth, lay, b_hit, cnt, ctl, 0, point_hits, st};
     // the launches are the render's (enqueue_tail / enqueue_iteration); the rows name the instances they take
-    if (mode == RT_STEP_TAIL) {
+    int extend_inst = EXTEND_PER_RAY;
+    if (mode == RT_STEP_FUSED) {
+        TRY(enqueue_iteration(*s, a, path, true, nullptr, &extend_inst));
+        if (extend_inst != EXTEND_CURVES_FUSED && extend_inst != EXTEND_CURVES_FUSED_EXACT)
+            return fail("internal: the fused curve extend was not launched");
+    } else if (mode == RT_STEP_TAIL) {
         const FinishInst fi = finish_instance(s->dev, rp, tree0_budget(*s));
         const int32_t row[6] = {1, fi.f, fi.tl, fi.ls, fi.solo ? 1 : 0, fi.ex ? 1 : 0};
         std::memcpy(out_inst, row, sizeof row);
@@ -347,8 +357,9 @@ int rt_step_rays(int scene, int n, const double* rays, const double* T_in, const
             const int32_t row[6] = {1, si.tl, si.ls, si.ll ? 1 : 0, si.ex ? 1 : 0, si.pt ? 1 : 0};
             std::memcpy(out_inst + 8 * mt, row, sizeof row);
         }
-        TRY(enqueue_iteration(*s, a, path, false, nullptr));
+        TRY(enqueue_iteration(*s, a, path, false, nullptr, &extend_inst));
     }
+    out_inst[7] = extend_inst;
     // read everything back
     h.cnt.resize(kCountsPerIter);
     p.later(h.cnt.data(), cnt, (size_t)kCountsPerIter);
@@ -372,7 +383,8 @@ int rt_step_rays(int scene, int n, const double* rays, const double* T_in, const
         out_status[k] = wrote ? RT_STEP_WROTE : 0;
         std::memcpy(out_color + 3 * k, &h.sb[3 * k], 3 * sizeof(double));
     }
-    if (mode == RT_STEP_TAIL) return 0;
+    if (mode == RT_STEP_FUSED) *out_survivors = (uint32_t)h_ctl[kCtlFuseSegs];
+    if (mode != RT_STEP_STEP) return 0;
     return unpack_step(s, lay, pt, h, out_status, out_ray, out_T, out_ctr, out_t, out_mat, out_survivors);
 }
 

@@ -104,14 +104,26 @@ int lanes_for(const Context& c, const DevScene& d) {
 // one-pass-at-a-time loop, main.scm:533-544).  RTAMD_CURVE_FUSE=0 / 1: never / always (A/B, tests).
 // (2^23 / 2^25: the same within noise at 32 and 256 spp, profiles/r06/fuse_max/)
 constexpr uint32_t kFuseMaxRays = 1u << 24;
-bool curve_fuse(const DevScene& d, const uint32_t n) {
-    if (!(curve_kernel_scene(d) && curve_persistent() && !d.has_perlin && !d.has_image_tex && d.light.type == LIGHT_OFF)) return false;
-    if (!d.fuse_ring || d.n_leaves >= (1 << kFuseLeafBits) - 1) return false;    // FuseHit packs leaf + 1 in 25 bits
+}  // namespace
+
+namespace rtamd {
+const char* curve_fuse_refusal(const DevScene& d, const uint32_t n) {
+    if (!curve_kernel_scene(d)) return "the scene's renders do not take the persistent curve kernel";
+    if (!curve_persistent()) return "RTAMD_CURVE_BLOCKS=0 selects the per-ray kernel";
+    if (d.has_perlin) return "the scene has Perlin textures";
+    if (d.has_image_tex) return "the scene has image textures";
+    if (d.light.type != LIGHT_OFF) return "the scene samples a light";
+    if (!d.fuse_ring) return "the scene has no hand-off ring";
+    if (d.n_leaves >= (1 << kFuseLeafBits) - 1) return "the scene has too many leaves";    // FuseHit packs leaf + 1 in 25 bits
     const char* e = std::getenv("RTAMD_CURVE_FUSE");   // read per render: tests switch it inside one process
-    if (e && e[0] == '0') return false;
-    if (e && e[0] == '1') return true;
-    return n <= kFuseMaxRays;
+    if (e && e[0] == '0') return "RTAMD_CURVE_FUSE=0";
+    if (e && e[0] == '1') return nullptr;
+    return n <= kFuseMaxRays ? nullptr : "the launch has more rays than the fused extend takes";
 }
+}  // namespace rtamd
+
+namespace {
+bool curve_fuse(const DevScene& d, const uint32_t n) { return curve_fuse_refusal(d, n) == nullptr; }
 
 // What every render checks first.  render_sel runs it ahead of its own checks, so the same error wins
 // however the pixels are given.
@@ -125,7 +137,8 @@ int check_render(const Scene* s, int nx, int ny, int spp_begin, int spp_count) {
 }  // namespace
 
 namespace rtamd {
-int enqueue_iteration(const Scene& s, const StepArgs& a, const ExtendPath path, const bool may_fuse, const hipEvent_t* ev) {
+int enqueue_iteration(const Scene& s, const StepArgs& a, const ExtendPath path, const bool may_fuse, const hipEvent_t* ev,
+                      int* extend_inst) {
     const HitBuf hit = hit_buf(a.hit, a.lay);
     const uint32_t shard_cap = (uint32_t)a.lay.shard_cap;
     const bool pt = point_records(a.point_hits, path);
@@ -148,7 +161,7 @@ int enqueue_iteration(const Scene& s, const StepArgs& a, const ExtendPath path, 
         fused = may_fuse && a.depth > 0 && curve_fuse(s.dev, a.n);
         HIPCHK(launch_extend(dl, s.d_dev.as<const DevScene>(), a.rp, a.cur, a.in, a.n, hit, shard_cap, a.counts,
                              a.depth == 0, reinterpret_cast<unsigned int*>(a.ctl + kCtlClaim),
-                             fused ? &fz : nullptr, a.stream));
+                             fused ? &fz : nullptr, a.stream, extend_inst));
     }
     if (ev) HIPCHK(hipEventRecord(ev[1], a.stream));
     for (int mt = 0; mt < 4 && !fused; ++mt) {         // (a fused launch shades its hits itself: no queues)

@@ -368,7 +368,9 @@ def light_probe(scene, points, seed, dirs=None, ctx=None):
 
 #: rt_step_rays' extends, modes and status bit (include/rt.h)
 STEP_EXTEND_HBM, STEP_EXTEND_LDS = 0, 1
-STEP_STEP, STEP_TAIL = 0, 1
+STEP_STEP, STEP_TAIL, STEP_FUSED = 0, 1, 2
+#: StepResult.extend: the extend launch_extend took
+EXTEND_PER_RAY, EXTEND_CURVES, EXTEND_CURVES_FUSED, EXTEND_CURVES_FUSED_EXACT = 0, 1, 2, 3
 STEP_WROTE = 256
 STEP_SENTINEL = 0x7FF8DEAD5CA77E12
 
@@ -377,8 +379,10 @@ class StepResult:
     """rt_step_rays' outputs.  status (n,) int32: survivor entries of the record | STEP_WROTE; color (n, 3) the
     record's sample slot; ray (n, 6), T (n, 3), ctr (n,) the survivor; t (n,), mat (n,) the queued hit (-1: none);
     survivors: the device's survivor count; shade: {material type: (TL, LS, LL, EX, PT)} of the k_shade
-    instances launched (STEP); finish: (F, TL, LS, SOLO, EX) of the k_finish instance (TAIL), else None."""
-    __slots__ = ("status", "color", "ray", "T", "ctr", "t", "mat", "survivors", "shade", "finish")
+    instances launched (STEP); finish: (F, TL, LS, SOLO, EX) of the k_finish instance (TAIL), else None; extend:
+    the extend launched (EXTEND_*; STEP with the HBM extend, FUSED).  FUSED: status and color as for TAIL, and
+    survivors holds the continuation segments the fused launch counted."""
+    __slots__ = ("status", "color", "ray", "T", "ctr", "t", "mat", "survivors", "shade", "finish", "extend")
 
     def wrote(self):
         return (self.status & STEP_WROTE) != 0
@@ -413,8 +417,10 @@ def step_rays(scene, rays, T_in=None, ctr_in=None, pix=None, seed=0, smp=0, dept
          res.T.ctypes.data_as(dp), res.ctr.ctypes.data_as(up), res.t.ctypes.data_as(dp), res.mat.ctypes.data_as(ip),
          inst.ctypes.data_as(ip), ctypes.byref(surv))
     res.survivors = int(surv.value)
-    res.shade, res.finish = {}, None
-    if n and mode == STEP_TAIL:
+    res.shade, res.finish, res.extend = {}, None, int(inst[7])
+    if n and mode == STEP_FUSED:
+        pass
+    elif n and mode == STEP_TAIL:
         res.finish = (int(inst[1]), int(inst[2]), int(inst[3]), bool(inst[4]), bool(inst[5]))
     elif n:
         res.shade = {m: (int(inst[8 * m + 1]), int(inst[8 * m + 2]), bool(inst[8 * m + 3]), bool(inst[8 * m + 4]),

@@ -474,37 +474,9 @@ def test_curve_kernels_bitwise(sched, monkeypatch, flat_curves):
     flat list's per-lane test and the batched stage A/B must agree on them.
     (The C5 fault that the leaf-level clamp fixed did not reproduce at this
     size, so this is a parity check for the case, not that fault's replay.)"""
-    from rtamd import scene as g, vec as v
-    from rtamd.rng import HostStream
-    import numpy as np
+    import curve_step_cases
     nx, ny, spp = 40, 40, 2
-    rr = HostStream(0x5EED0103)
-    red = g.make_lambertian(g.constant_texture(v.vec3(0.65, 0.05, 0.05)))
-    white = g.make_lambertian(g.constant_texture(v.vec3(0.73, 0.73, 0.73)))
-    metal = g.make_metal(g.constant_texture(v.vec3(0.8, 0.8, 0.7)), 0.1)
-    glass = g.make_dielectric(1.5)
-    light = g.make_diffuse_light(g.constant_texture(v.vec3(4, 4, 4)))
-    objs = [g.flip_normals(g.make_yz_rect(0, 555, 0, 555, 555, white)),
-            g.make_xz_rect(0, 555, 0, 555, 0, white)]
-    objs.append(g.bezier_array(scenes.random_polyline_curves(600), 3.0, red))
-    if flat_curves:                  # 20000 tiny curves through the volume, extent ~0.5: half bent
-        rs = np.random.default_rng(0x5EED0104)   # by ~1e-3 (maxd -2..-4 at width 6), half straight
-        base = rs.uniform(20.0, 535.0, size=(20000, 1, 3))      # (l0 = rounding only, maxd ~ -20)
-        t = np.linspace(0.0, 0.5, 4).reshape(1, 4, 1) * rs.normal(size=(20000, 1, 3))
-        bend = 1e-3 * rs.normal(size=(20000, 4, 3))
-        bend[:10000] = 0.0
-        objs.append(g.bezier_array((base + t + bend).reshape(20000, 12), 6.0, white))
-    for i in range(40):
-        c = v.vec3(60 + rr() * 430, 40 + rr() * 400, 60 + rr() * 430)
-        m = (white, metal, glass)[i % 3]
-        if i % 4 == 0:
-            objs.append(g.make_moving_sphere(c, v.vec3(c[0], c[1] + 20, c[2]), 0.0, 1.0, 15 + 10 * rr(), m))
-        else:
-            objs.append(g.make_sphere(c, 10 + 15 * rr(), m))
-    objs += [g.flip_normals(g.make_xz_rect(213, 343, 227, 332, 554, light)),
-             g.make_yz_rect(0, 555, 0, 555, 0, red),
-             g.flip_normals(g.make_xy_rect(0, 555, 0, 555, 555, white))]
-    sc = g.make_scene(objs, scenes.cornell_camera_for(nx, ny), g.sky_color)
+    sc = curve_step_cases.curve_mix_scene(nx, ny, flat_curves)      # (the step probe's records run on it too)
     sched.set_option("tail_off", 1)
     imgs = []
     # the flat list, the per-ray kernel, the persistent curve extend fused over the depths (the default: hits

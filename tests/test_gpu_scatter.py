@@ -475,7 +475,9 @@ def test_refusals(sched):
     with pytest.raises(RtError, match="unknown extend"):
         gpu.step_rays(scene, rays, extend=2)
     with pytest.raises(RtError, match="unknown mode"):
-        gpu.step_rays(scene, rays, mode=2)
+        gpu.step_rays(scene, rays, mode=3)
+    with pytest.raises(RtError, match="would not take the fused curve extend"):     # RT_STEP_FUSED: curve-kernel scenes only
+        gpu.step_rays(scene, rays, depth=1, mode=gpu.STEP_FUSED)
     with pytest.raises(RtError, match="throughput 1"):
         gpu.step_rays(scene, rays, T_in=np.full((8, 3), 0.5), depth=0)
     bad = rays.copy()
@@ -489,8 +491,10 @@ def test_refusals(sched):
         gpu.step_rays(scene, rays, depth=1, extend=LDS)
     with pytest.raises(RtError, match="depth >= 1"):
         gpu.step_rays(_solo(), sc.recs_solo()[:8], depth=0, extend=LDS)
-    with pytest.raises(RtError, match="persistent curve kernel"):
-        gpu.step_rays(scenes.cornell_curves_small(16, 16), rays, depth=1)
+    # scenes whose renders take the persistent curve kernel are stepped through it (tests/test_gpu_curve_step.py)
+    r = gpu.step_rays(scenes.cornell_curves_small(16, 16), rays, depth=1)
+    assert r.extend == gpu.EXTEND_CURVES and ((r.entries() + r.wrote()) == 1).all()
+    assert gpu.step_rays(scene, rays, depth=1).extend == gpu.EXTEND_PER_RAY
     # null pointers, n < 0, an uncommitted scene: through the ABI itself
     h = gpu.upload(scene)
     L = _lib.lib()
