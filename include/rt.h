@@ -221,16 +221,41 @@ int rt_add_bvh(int scene, const int* objs, int n, double time0, double time1, in
  *   - the point is o + d * t on the instance-local ray, as for every leaf;
  *   - the normal is the geometric one, formed once at the commit: e1 = v1 - v0, e2 = v2 - v0, n = cross(e1, e2),
  *     normal = n * (1.0 / sqrt(dot(n, n))).  rt_add_flip_normals negates it; the instance chain takes point and
- *     normal back out as for rects.  There are no per-vertex shading normals;
+ *     normal back out as for rects.  A mesh with vertex normals replaces it (shading normals, below);
  *   - u, v (read by image textures only): with texture coordinates (u0, v0), (u1, v1), (u2, v2) of the vertices,
  *     w = pt - v0, b1 = dot(cross(w, e2), n) / dot(n, n), b2 = dot(cross(e1, w), n) / dot(n, n),
  *     b0 = (1.0 - b1) - b2, u = (b0 * u0 + b1 * u1) + b2 * u2, and v alike.  Without texture coordinates
  *     u = v = 0, as for curves.
- * rtamd.mesh restates all of this in NumPy (hit, normal, uv). */
+ *
+ * Shading normals (RT_HAS_SMOOTH_NORMALS).  rt_add_mesh_normals is rt_add_mesh with one normal per vertex
+ * (normals = nv x {x, y, z}); with normals = NULL it is rt_add_mesh, bit for bit.  At the add call each normal
+ * is made unit: nk = n * (1.0 / sqrt(dot(n, n))).  Refused there, as rt_add_mesh refuses (before the handle
+ * is looked at, the scene left as it was, the message naming the face): a normal of a face's vertex that is not
+ * finite, or whose length is zero or not finite.
+ * For a hit at the local point pt on a triangle with unit vertex normals n0, n1, n2, componentwise and in IEEE
+ * f64 in exactly this order, no operation contracted into an FMA:
+ *     w = pt - v0;  b1 = dot(cross(w, e2), n) / dot(n, n);  b2 = dot(cross(e1, w), n) / dot(n, n)
+ *                                                    (the barycentrics of u, v above: formed once per record)
+ *     s = (n0 + (n1 - n0) * b1) + (n2 - n0) * b2
+ *     q = dot(s, s)
+ *     normal = s * (1.0 / sqrt(q)) if q > 0 and q is finite, else the geometric normal
+ * The difference form gives n0 back exactly where the three normals are equal.  The shading normal replaces the
+ * geometric normal in the hit record and nowhere else: the hit test, the leaf boxes, the ties and a triangle
+ * light's density and area (light lists, below) keep the geometric triangle.  rt_add_flip_normals negates the
+ * shading normal and the instance chain takes it out as it takes any normal out; it is neither renormalised
+ * nor turned to face the ray: the vertex normals say which side is outside, as the winding does for a flat
+ * triangle.  Two consequences: a diffuse_light emits on the shading normal's side (dot(normal, d) < 0), which
+ * near a silhouette is not the geometric side; and a lambertian bounce, drawn about the shading normal, may
+ * start below the geometric surface (and then hits the mesh again from inside, or leaves through it).
+ * rt_add_triangle has no normals argument.
+ * rtamd.mesh restates all of this in NumPy (hit, normal, uv, shading_normal). */
 #define RT_HAS_TRIANGLES 1
+#define RT_HAS_SMOOTH_NORMALS 1
 int rt_add_triangle(int scene, const double v0[3], const double v1[3], const double v2[3], int mat, int* out_obj);
 int rt_add_mesh(int scene, const double* verts, int nv, const int32_t* faces, int nf, const double* uv, int mat,
                 int* out_obj);
+int rt_add_mesh_normals(int scene, const double* verts, int nv, const int32_t* faces, int nf, const double* uv,
+                        const double* normals /* nv x 3, nullable */, int mat, int* out_obj);
 
 /* camera — cam:make-camera (camera.scm:63-78) evaluated on the host side;
  * the 24 doubles are the 10 slots the reference's get-ray reads. */

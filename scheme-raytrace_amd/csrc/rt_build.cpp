@@ -69,6 +69,12 @@ TriUv tri_uv(const Obj& o) {
     for (int k = 0; k < 3; ++k) { q.u[k] = o.uv[k]; q.v[k] = o.uv[3 + k]; }
     return q;
 }
+TriNrm tri_nrm(const Obj& o) {
+    TriNrm q{};
+    q.has = o.has_nrm ? 1 : 0;
+    for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) q.n[i][k] = o.nrm[3 * i + k];
+    return q;
+}
 // the extend-side part of a leaf's LeafInfo, all but `local` (shade_fields adds the rest); a triangle's
 // normal is formed here, once (tri_normal: a degenerate one, refused by the add calls, keeps 0 0 0)
 LeafInfo leaf_info(const LeafTmp& L, const Obj& o) {
@@ -394,7 +400,7 @@ void put_record(const SceneDesc& s, const LeafTmp& L, const int pos, const int l
     case LEAF_MSPHERE: h.msph[k] = msphere_rec(o); ll.msph[k] = li; break;
     case LEAF_BEZIER: h.bez[k] = bezier_rec(o, (uint32_t)std::max(pos, 0)); ll.bez[k] = li; break;   // (boundaries hold no curves)
     case LEAF_KLEIN: h.klein[k] = KleinRec{o.c0[0], o.c0[1], o.c0[2], 0.0}; ll.klein[k] = li; break;
-    case LEAF_TRI: h.tri[k] = tri_rec(o); h.triuv[k] = tri_uv(o); ll.tri[k] = li; break;
+    case LEAF_TRI: h.tri[k] = tri_rec(o); h.triuv[k] = tri_uv(o); h.trinrm[k] = tri_nrm(o); ll.tri[k] = li; break;
     default: h.rect[k] = rect_rec(o); ll.rect[k] = li;           // the three axis types share the rect array
     }
     if (pos < 0) return;
@@ -404,7 +410,7 @@ void put_record(const SceneDesc& s, const LeafTmp& L, const int pos, const int l
 // one more slot at the end of a type's arrays: its index
 int grow(HostScene& h, const int type) {
     auto one = [](auto& recs, auto& infos) { recs.resize(recs.size() + 1); infos.resize(recs.size()); return (int)recs.size() - 1; };
-    if (type == LEAF_TRI) { h.triuv.resize(h.tri.size() + 1); return one(h.tri, h.ll.tri); }
+    if (type == LEAF_TRI) { h.triuv.resize(h.tri.size() + 1); h.trinrm.resize(h.tri.size() + 1); return one(h.tri, h.ll.tri); }
     return type == LEAF_SPHERE ? one(h.sph, h.ll.sph) : type == LEAF_MSPHERE ? one(h.msph, h.ll.msph)
          : type == LEAF_BEZIER ? one(h.bez, h.ll.bez) : type == LEAF_KLEIN ? one(h.klein, h.ll.klein) : one(h.rect, h.ll.rect);
 }
@@ -661,7 +667,7 @@ int assign_leaf_ids(const int threads, HostScene& h, std::string& err) {
     const LeafLists& ll = h.ll;
     if (ll.sph.size() != h.sph.size() || ll.msph.size() != h.msph.size() || ll.bez.size() != h.bez.size() ||
         ll.klein.size() != h.klein.size() || ll.rect.size() != h.rect.size() || ll.tri.size() != h.tri.size() ||
-        h.triuv.size() != h.tri.size())
+        h.triuv.size() != h.tri.size() || h.trinrm.size() != h.tri.size())
         return fail_with(&err, "internal: leaf records and leaf infos out of step");
     int32_t* base = h.d.leaf_base;
     base[LEAF_SPHERE] = 0;
@@ -820,6 +826,7 @@ void scene_fields(const SceneDesc& s, const BuildOptions& opt, const bool tree0_
     d.n_sph = (int)h.sph.size(); d.n_msph = (int)h.msph.size(); d.n_rect = (int)h.rect.size();
     d.n_bez = (int)h.bez.size(); d.n_klein = (int)h.klein.size(); d.n_med = (int)h.med.size();
     d.n_tri = (int)h.tri.size();
+    for (const TriNrm& q : h.trinrm) if (q.has) { d.tri_smooth = 1; break; }
     d.n_groups = (int)h.groups.size(); d.n_bgroups = (int)h.bgroups.size();
     d.n_chains = (int)h.chains.size(); d.n_leaves = (int)h.leaves.size();
     d.n_bvh2 = (int)h.bvh2.size(); d.n_bleaf = (int)h.bleaf.size();

@@ -79,8 +79,9 @@ struct HostScene {
     HostVec<BezierRec> bez;
     std::vector<KleinRec> klein;
     std::vector<MediumRec> med;
-    std::vector<TriRec> tri;                         // triangles, in tree order, and their texture coordinates
-    std::vector<TriUv> triuv;
+    std::vector<TriRec> tri;                         // triangles, in tree order, their texture coordinates and
+    std::vector<TriUv> triuv;                        // their vertices' shading normals, one of each per triangle
+    std::vector<TriNrm> trinrm;
     std::vector<Group> groups, bgroups;
     HostVec<BvhNode2> bvh2, fbvh2, g0bvh2;           // the world tree; the time-0 tree, sphere form / generic form
     HostVec<BvhLeaf> bleaf, fbleaf, g0bleaf;

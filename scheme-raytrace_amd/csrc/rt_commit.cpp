@@ -191,6 +191,7 @@ int commit_scene(Scene* s, int world) {
     up(s->d_g0bleaf, h.g0bleaf, &DevScene::g0bleaf, "g0bleaf", gtree0);
     up(s->d_tri, h.tri, &DevScene::tri, "tri", !h.tri.empty());
     up(s->d_triuv, h.triuv, &DevScene::triuv, "triuv", !h.tri.empty());
+    up(s->d_trinrm, h.trinrm, &DevScene::trinrm, "trinrm", h.d.tri_smooth != 0);   // (read behind tri_smooth only)
     up(s->d_lights, h.lights, &DevScene::lights, "lights", !h.lights.empty());
     up(s->d_mats, s->mats, &DevScene::mats, "mats");
     up(s->d_texs, s->texs, &DevScene::texs, "texs");

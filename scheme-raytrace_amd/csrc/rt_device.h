@@ -58,6 +58,10 @@ struct alignas(64) RectRec { double a0, a1, b0, b1, k, pad0, pad1, pad2; };
 struct alignas(32) TriRec { double v0[3], v1[3], v2[3], pad0, pad1, pad2; };
 // Its texture coordinates, read by hit_uv only (DevScene::triuv, one per TriRec): has = 0: none, u = v = 0
 struct alignas(8) TriUv { double u[3], v[3]; int32_t has, pad; };
+// Its vertices' unit shading normals n0, n1, n2, read by hit_record_at only (DevScene::trinrm, one per TriRec):
+// has = 0: none, the hit record keeps the geometric normal
+struct alignas(8) TriNrm { double n[3][3]; int32_t has, pad; };
+static_assert(sizeof(TriNrm) == 80, "TriNrm layout");
 // Cubic Bezier curve of a given width (bezier.scm:61-66): control points,
 // width1 = width/2, width2 = width1^2, eps8 = 8*(width/20).
 // order: the curve's position in the flattened object list (ties between curves at one z go to the later one)
@@ -248,6 +252,10 @@ struct DevScene {
     // A list of one rect or sphere is `light` itself, with n_lights 0.
     const DevLightRec* lights; int32_t n_lights;
     int32_t lights_tri;                        // 1: some light of the list is a triangle
+    // Per-vertex shading normals (include/rt.h, "triangles"), one record per TriRec; tri_smooth = 1: some record
+    // has them (wave-uniform: a scene without any never reads trinrm)
+    const TriNrm* trinrm;
+    int32_t tri_smooth;
 };
 
 // Wavefront path state, SoA, one slot per live path (ping-pong buffers).

@@ -147,7 +147,7 @@ struct Scene : SceneDesc {       // the builder's record (rt_model.h) and what a
     DevBuf d_order;
     DevBuf d_teximg;                               // the image textures' texels
     DevBuf d_gleaf, d_leaf_pos, d_g0bvh2, d_g0bleaf, d_rot;   // generic tree leaves (DevScene::gleaf)
-    DevBuf d_tri, d_triuv;                         // triangles and their texture coordinates (DevScene::tri)
+    DevBuf d_tri, d_triuv, d_trinrm;               // triangles, their texture coordinates and shading normals (DevScene::tri)
     DevBuf d_lights;                               // the light list's records (DevScene::lights)
     rt_tree_info tree{};                           // rt_get_tree_info's record, filled by commit_scene
     size_t ext_lds = 0;                            // k_extend_lds: LDS bytes (0 = not used) and grid cap

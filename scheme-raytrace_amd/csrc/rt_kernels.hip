@@ -2947,8 +2947,43 @@ __device__ __noinline__ void sphere_uv(const v3 n, double& u, double& v) {
     u = 1.0 - (phi + kPi) / (2.0 * kPi);
     v = (theta + kPi / 2.0) / kPi;
 }
+// A triangle's barycentrics b1, b2 of the point pt (include/rt.h, "triangles"): formed once per hit record, for
+// the texture coordinates and the shading normal alike
+struct TriBary { bool have = false; double b1 = 0.0, b2 = 0.0; };
+__device__ __forceinline__ TriBary tri_bary(const TriRec* __restrict__ tp, const v3 pt) {
+    const TriRec T = *tp;
+    const v3 v0 = mk(T.v0[0], T.v0[1], T.v0[2]);
+    const v3 e1 = mk(T.v1[0], T.v1[1], T.v1[2]) - v0, e2 = mk(T.v2[0], T.v2[1], T.v2[2]) - v0;
+    const v3 nn = cross(e1, e2), w = pt - v0;
+    const double den = dot(nn, nn);
+    TriBary B;
+    B.have = true;
+    B.b1 = dot(cross(w, e2), nn) / den;
+    B.b2 = dot(cross(e1, w), nn) / den;
+    return B;
+}
+// The shading normal of a smooth triangle at pt (include/rt.h, "triangles": shading normals) with the barycentrics
+// it formed (tri_bary); geo: the geometric normal, returned where s has no direction.
+// A call, not inlined (the sphere_uv precedent): inlined, the two records' loads cost every k_shade 1 to 4 VGPRs
+// whether or not a hit is on a smooth triangle, and took the plain lambertian shade from 127 to 129 (4 waves per
+// SIMD to 3) and the Perlin one from 168 to 169 (3 to 2); out of line the callers keep their VGPRs, with no scratch
+// (profiles/smooth_normals/kernel_resources_vs_parent.txt)
+struct SmoothNrm { v3 n; TriBary tb; };
+__device__ __noinline__ SmoothNrm tri_smooth_normal(const TriRec* __restrict__ tp, const TriNrm* __restrict__ np, const v3 pt, const v3 geo) {
+    SmoothNrm S;
+    S.tb = tri_bary(tp, pt);
+    const TriNrm N = *np;
+    const v3 n0 = mk(N.n[0][0], N.n[0][1], N.n[0][2]);
+    const v3 n1 = mk(N.n[1][0], N.n[1][1], N.n[1][2]), n2 = mk(N.n[2][0], N.n[2][1], N.n[2][2]);
+    const v3 sn = (n0 + (n1 - n0) * S.tb.b1) + (n2 - n0) * S.tb.b2;
+    const double q = dot(sn, sn);
+    S.n = (q > 0.0 && q < __builtin_huge_val()) ? sn * (1.0 / sqrt(q)) : geo;
+    return S;
+}
+// tb: the triangle's barycentrics where hit_record_at has formed them already (a smooth triangle)
 template <bool TRI>
-__device__ __forceinline__ void hit_uv(const DevScene& sc, const LeafInfo& li, const v3 pt, const v3 n, double& u, double& v) {
+__device__ __forceinline__ void hit_uv(const DevScene& sc, const LeafInfo& li, const v3 pt, const v3 n, TriBary tb,
+                                       double& u, double& v) {
     u = 0.0; v = 0.0;
     if (li.type == LEAF_SPHERE || li.type == LEAF_MSPHERE) {
         sphere_uv(n, u, v);
@@ -2962,12 +2997,8 @@ __device__ __forceinline__ void hit_uv(const DevScene& sc, const LeafInfo& li, c
         // include/rt.h, "triangles": the vertices' texture coordinates weighted by the point's barycentrics
         const TriUv Q = sc.triuv[li.local];
         if (Q.has) {
-            const TriRec T = sc.tri[li.local];
-            const v3 v0 = mk(T.v0[0], T.v0[1], T.v0[2]);
-            const v3 e1 = mk(T.v1[0], T.v1[1], T.v1[2]) - v0, e2 = mk(T.v2[0], T.v2[1], T.v2[2]) - v0;
-            const v3 nn = cross(e1, e2), w = pt - v0;
-            const double den = dot(nn, nn);
-            const double b1 = dot(cross(w, e2), nn) / den, b2 = dot(cross(e1, w), nn) / den;
+            if (!tb.have) tb = tri_bary(sc.tri + li.local, pt);
+            const double b1 = tb.b1, b2 = tb.b2;
             const double b0 = (1.0 - b1) - b2;
             u = (b0 * Q.u[0] + b1 * Q.u[1]) + b2 * Q.u[2];
             v = (b0 * Q.v[0] + b1 * Q.v[1]) + b2 * Q.v[2];
@@ -3192,6 +3223,7 @@ __device__ __forceinline__ v3 light_random(const DevLightRec* __restrict__ recs,
 template <int TL, bool TRI = true>
 __device__ __forceinline__ void hit_record_at(const DevScene& sc, const LeafInfo& li, const v3 d, const double time,
                                               const v3 pt, v3& nrm, double& tu, double& tv) {
+    [[maybe_unused]] TriBary tb;
     if (li.type == LEAF_SPHERE) {
         nrm = (pt - mk(li.c[0], li.c[1], li.c[2])) * li.inv_r;
     } else if (li.type == LEAF_MSPHERE) {
@@ -3214,12 +3246,19 @@ __device__ __forceinline__ void hit_record_at(const DevScene& sc, const LeafInfo
         nrm = klein_normal(mk(K.cx, K.cy, K.cz), pt);        // at ray-pos = point-at-parameter, :664
     } else if (TRI && li.type == LEAF_TRI) {
         nrm = mk(li.c[0], li.c[1], li.c[2]);                 // the geometric normal, formed at the commit
+        // per-vertex shading normals: the records are loaded behind the flags (in tri_smooth_normal), so that a
+        // flat triangle and every other leaf pay the tests only
+        if (sc.tri_smooth && sc.trinrm[li.local].has) {
+            const SmoothNrm S = tri_smooth_normal(sc.tri + li.local, sc.trinrm + li.local, pt, nrm);
+            nrm = S.n;
+            tb = S.tb;
+        }
     } else {
         nrm = d * -1.0;                                      // curve: (v:scale (dir r) -1), bezier.scm:204
     }
     tu = 0.0; tv = 0.0;                                      // the record's u, v: read by image textures only
     if constexpr (TL >= kTexImage) {
-        if (li.tex_kind == TK_GENERIC) hit_uv<TRI>(sc, li, pt, nrm, tu, tv);
+        if (li.tex_kind == TK_GENERIC) hit_uv<TRI>(sc, li, pt, nrm, tb, tu, tv);
     }
     if (li.flip) nrm = nrm * -1.0;                          // flip-normals :438
 }

@@ -24,6 +24,8 @@ struct Obj {
     double width = 0;
     double uv[6] = {0};        // O_TRI: u0, u1, u2, v0, v1, v2 of its vertices (has_uv)
     bool has_uv = false;
+    double nrm[9] = {0};       // O_TRI: the unit shading normals n0, n1, n2 of its vertices (has_nrm)
+    bool has_nrm = false;
 };
 
 // A triangle's unit geometric normal (include/rt.h, "triangles"): n = cross(v1 - v0, v2 - v0) scaled by

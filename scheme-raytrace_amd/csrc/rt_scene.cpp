@@ -302,23 +302,39 @@ int rt_add_triangle(int scene, const double v0[3], const double v1[3], const dou
     o.mat = mat;
     return push_obj(s, std::move(o), out);
 }
-int rt_add_mesh(int scene, const double* verts, int nv, const int32_t* faces, int nf, const double* uv, int mat, int* out) {
+// rt_add_mesh and rt_add_mesh_normals (fn: the caller's name in the messages; normals = nullptr: a flat mesh)
+static int add_mesh(const char* fn, int scene, const double* verts, int nv, const int32_t* faces, int nf, const double* uv,
+                    const double* normals, int mat, int* out) {
+    const std::string who = fn;
     OUT_OR_FAIL(out);
-    if (!verts || !faces) return fail("rt_add_mesh: null vertex or face array");
-    if (nv < 1 || nf < 1) return fail("rt_add_mesh: nv and nf must be at least 1");
+    if (!verts || !faces) return fail(who + ": null vertex or face array");
+    if (nv < 1 || nf < 1) return fail(who + ": nv and nf must be at least 1");
     // a face's triangle: its indices checked, its vertices and texture coordinates read (tri_obj's checks)
     auto face_obj = [&](const int f, Obj& o) {
         const int32_t* ix = faces + 3 * (size_t)f;
         for (int k = 0; k < 3; ++k)
             if (ix[k] < 0 || ix[k] >= nv)
-                return fail("rt_add_mesh: face " + std::to_string(f) + " has vertex index " + std::to_string(ix[k]) +
+                return fail(who + ": face " + std::to_string(f) + " has vertex index " + std::to_string(ix[k]) +
                             " out of range (" + std::to_string(nv) + " vertices)");
-        if (tri_obj("rt_add_mesh", verts + 3 * (size_t)ix[0], verts + 3 * (size_t)ix[1], verts + 3 * (size_t)ix[2], f, o)) return 1;
+        if (tri_obj(fn, verts + 3 * (size_t)ix[0], verts + 3 * (size_t)ix[1], verts + 3 * (size_t)ix[2], f, o)) return 1;
         if (uv) {
             o.has_uv = true;
             for (int k = 0; k < 3; ++k) { o.uv[k] = uv[2 * (size_t)ix[k]]; o.uv[3 + k] = uv[2 * (size_t)ix[k] + 1]; }
             for (int k = 0; k < 6; ++k)
-                if (!std::isfinite(o.uv[k])) return fail("rt_add_mesh: face " + std::to_string(f) + " has a texture coordinate that is not finite");
+                if (!std::isfinite(o.uv[k])) return fail(who + ": face " + std::to_string(f) + " has a texture coordinate that is not finite");
+        }
+        if (normals) {                                  // each made unit: nk = n * (1.0 / sqrt(dot(n, n)))
+            o.has_nrm = true;
+            for (int k = 0; k < 3; ++k) {
+                const double* n = normals + 3 * (size_t)ix[k];
+                if (!std::isfinite(n[0]) || !std::isfinite(n[1]) || !std::isfinite(n[2]))
+                    return fail(who + ": face " + std::to_string(f) + " has a vertex normal that is not finite");
+                const double len = std::sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+                if (!(len > 0.0) || !std::isfinite(len))
+                    return fail(who + ": face " + std::to_string(f) + " has a vertex normal of zero or non-finite length");
+                const double inv = 1.0 / len;
+                for (int c = 0; c < 3; ++c) o.nrm[3 * k + c] = n[c] * inv;
+            }
         }
         return 0;
     };
@@ -341,6 +357,13 @@ int rt_add_mesh(int scene, const double* verts, int nv, const int32_t* faces, in
         s->objs.push_back(std::move(o));
     }
     return push_obj(s, std::move(list), out);
+}
+int rt_add_mesh(int scene, const double* verts, int nv, const int32_t* faces, int nf, const double* uv, int mat, int* out) {
+    return add_mesh("rt_add_mesh", scene, verts, nv, faces, nf, uv, nullptr, mat, out);
+}
+int rt_add_mesh_normals(int scene, const double* verts, int nv, const int32_t* faces, int nf, const double* uv,
+                        const double* normals, int mat, int* out) {
+    return add_mesh("rt_add_mesh_normals", scene, verts, nv, faces, nf, uv, normals, mat, out);
 }
 int rt_add_klein(int scene, const double center[3], int mat, int* out) {
     SCENE_OR_FAIL(s, scene);

@@ -129,6 +129,8 @@ _SIGNATURES = {
     "rt_add_triangle": [ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int, _c_int_p],   # RT_HAS_TRIANGLES
     "rt_add_mesh": [ctypes.c_int, _c_double_p, ctypes.c_int, _c_i32_p, ctypes.c_int, _c_double_p, ctypes.c_int,
                     _c_int_p],
+    "rt_add_mesh_normals": [ctypes.c_int, _c_double_p, ctypes.c_int, _c_i32_p, ctypes.c_int, _c_double_p, _c_double_p,
+                            ctypes.c_int, _c_int_p],                                         # RT_HAS_SMOOTH_NORMALS
     "rt_add_flip_normals": [ctypes.c_int, ctypes.c_int, _c_int_p],
     "rt_add_constant_medium": [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_int_p],
     "rt_add_klein": [ctypes.c_int, _c_double_p, ctypes.c_int, _c_int_p],
@@ -215,6 +217,10 @@ _SIGNATURES = {
 
 #: every symbol include/rt.h declares (tests check the .so exports all of them)
 EXPORTED = sorted(list(_SIGNATURES) + ["rt_last_error"])
+#: entry points a library built from an earlier commit may lack when RTAMD_LIB names one for an A/B measurement
+#: (tools/smooth_normals_report.py --parent): lib() loads such a library without them, and calling one raises
+#: RtError.  The in-tree build must export them all (EXPORTED; __graft_entry__.build() checks it).
+OPTIONAL = frozenset(["rt_add_mesh_normals"])
 
 _lib = None
 
@@ -242,6 +248,8 @@ def lib():
             "(the GPU path has no fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
     for name, argtypes in _SIGNATURES.items():
+        if name in OPTIONAL and os.environ.get("RTAMD_LIB") and not hasattr(L, name):
+            continue
         fn = getattr(L, name)
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int
@@ -258,7 +266,10 @@ def check(status):
 
 
 def call(name, *args):
-    check(getattr(lib(), name)(*args))
+    fn = getattr(lib(), name, None) if name in OPTIONAL else getattr(lib(), name)
+    if fn is None:
+        raise RtError("%s does not export %s (a library built before that entry point existed)" % (LIB_PATH, name))
+    check(fn(*args))
 
 
 def dvec(values):

@@ -149,8 +149,9 @@ class GpuBuilder:
     def triangle(self, a, b, c, mat):
         return self._out("rt_add_triangle", dvec(a), dvec(b), dvec(c), mat)
 
-    def mesh(self, verts, faces, uvs, mat):
-        """verts (nv, 3) float64, faces (nf, 3) int32, uvs (nv, 2) float64 or None; returns the mesh's list object."""
+    def mesh(self, verts, faces, uvs, mat, normals=None):
+        """verts (nv, 3) float64, faces (nf, 3) int32, uvs (nv, 2) float64 or None, normals (nv, 3) float64 or
+        None (rt_add_mesh_normals); returns the mesh's list object."""
         verts = np.ascontiguousarray(verts, dtype=np.float64)
         faces = np.ascontiguousarray(faces, dtype=np.int32)
         dp = ctypes.POINTER(ctypes.c_double)
@@ -158,6 +159,13 @@ class GpuBuilder:
         if uvs is not None:
             uvs = np.ascontiguousarray(uvs, dtype=np.float64)
             uv = uvs.ctypes.data_as(dp)
+        if normals is not None:
+            normals = np.ascontiguousarray(normals, dtype=np.float64)
+            if normals.shape != (verts.shape[0], 3):
+                raise ValueError("mesh: normals must have shape (nv, 3)")
+            return self._out("rt_add_mesh_normals", verts.ctypes.data_as(dp), int(verts.shape[0]),
+                             faces.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(faces.shape[0]), uv,
+                             normals.ctypes.data_as(dp), mat)
         return self._out("rt_add_mesh", verts.ctypes.data_as(dp), int(verts.shape[0]),
                          faces.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(faces.shape[0]), uv, mat)
 

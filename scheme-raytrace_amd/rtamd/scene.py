@@ -98,11 +98,14 @@ def make_diffuse_light(emit):
 
 
 class Hitable:
-    __slots__ = ("kind", "args")
+    # normals: a mesh's per-vertex shading normals (nv, 3) or None, carried beside args (a mesh's args stay
+    # (vertices, faces, uvs, material))
+    __slots__ = ("kind", "args", "normals")
 
     def __init__(self, kind, *args):
         self.kind = kind
         self.args = args
+        self.normals = None
 
     def __repr__(self):
         return "#<hitable %s>" % self.kind
@@ -177,10 +180,12 @@ def make_triangle(a, b, c, material):
     return Hitable("triangle", a, b, c, material)
 
 
-def make_mesh(vertices, faces, material, uvs=None):
-    """A triangle mesh (include/rt.h, rt_add_mesh): ``vertices`` (nv, 3), ``faces`` (nf, 3) vertex indices,
-    ``uvs`` (nv, 2) texture coordinates or None (then u = v = 0).  Behaves as the list of its triangles in
-    face order, so it goes under translate / rotate_y / flip_normals like any hitable."""
+def make_mesh(vertices, faces, material, uvs=None, normals=None):
+    """A triangle mesh (include/rt.h, rt_add_mesh / rt_add_mesh_normals): ``vertices`` (nv, 3), ``faces``
+    (nf, 3) vertex indices, ``uvs`` (nv, 2) texture coordinates or None (then u = v = 0), ``normals`` (nv, 3)
+    per-vertex shading normals or None (then the mesh is shaded flat).  Behaves as the list of its triangles in
+    face order, so it goes under translate / rotate_y / flip_normals like any hitable.  The normals are the
+    Hitable's ``normals`` attribute; its ``args`` are (vertices, faces, uvs, material) either way."""
     import numpy as np
     from . import mesh as _mesh
     _need(material, Material, "make-mesh material")
@@ -195,7 +200,14 @@ def make_mesh(vertices, faces, material, uvs=None):
         if uvs.shape != (vs.shape[0], 2):
             raise ValueError("make-mesh: uvs must have shape (nv, 2)")
     _mesh.check_triangles(vs, fs, "make-mesh")
-    return Hitable("mesh", vs, fs, uvs, material)
+    h = Hitable("mesh", vs, fs, uvs, material)
+    if normals is not None:
+        normals = np.ascontiguousarray(normals, dtype=np.float64)
+        if normals.shape != (vs.shape[0], 3):
+            raise ValueError("make-mesh: normals must have shape (nv, 3)")
+        _mesh.check_normals(normals, fs, "make-mesh")
+        h.normals = normals
+    return h
 
 
 def make_klein(center, material):
@@ -420,7 +432,12 @@ def emit(scene, b):
                 raise NotImplementedError(
                     "triangles are not restated in %s (only the GPU builder takes them; rtamd.mesh is their "
                     "NumPy restatement)" % type(b).__name__)
-            r = b.triangle(a[0], a[1], a[2], mat(a[3])) if o.kind == "triangle" else b.mesh(a[0], a[1], a[2], mat(a[3]))
+            if o.kind == "triangle":
+                r = b.triangle(a[0], a[1], a[2], mat(a[3]))
+            elif o.normals is None:
+                r = b.mesh(a[0], a[1], a[2], mat(a[3]))
+            else:
+                r = b.mesh(a[0], a[1], a[2], mat(a[3]), normals=o.normals)
         elif o.kind == "medium":
             r = b.constant_medium(obj(a[0]), a[1], tex(a[2]))
         elif o.kind == "flip":

@@ -181,6 +181,19 @@ def cornell_mesh_lights(nx, ny):
     return g.make_scene(sc.obj_list, sc.camera, sc.sky_function, lights=[sc.obj_list[2]])
 
 
+def cornell_smooth(nx, ny, level=3, smooth=True):
+    """The lifted room (cornell_lifted's six rects, no boxes) with a metal ball of radius 90 standing on the floor:
+    an icosphere(level) with radial vertex normals (include/rt.h, "triangles": shading normals), so it reflects as
+    a sphere does.  smooth=False: the same mesh shaded flat, every facet a mirror."""
+    from . import mesh
+    objs = list(cornell_lifted(nx, ny).obj_list[:6])
+    center = (190.0, 91.0, 190.0)
+    vs, fs = mesh.icosphere(level, 90.0, center)
+    metal = g.make_metal(g.constant_texture(v.vec3(0.8, 0.85, 0.88)), 0.0)
+    objs.append(g.make_mesh(vs, fs, metal, normals=mesh.radial_normals(vs, center) if smooth else None))
+    return g.make_scene(objs, cornell_camera_for(nx, ny), g.sky_color)
+
+
 def cornell_image_textures(floor_size=(64, 64), wall_size=(32, 32)):
     """cornell_image's two images, generated from formulas: the floor a grid of warm tiles with dark joints,
     the back wall a smooth two-way colour ramp.  Returns (floor, wall) image textures."""
@@ -484,6 +497,7 @@ SCENES = {
     "cornell_lifted": cornell_lifted,
     "cornell_mesh": cornell_mesh,
     "cornell_mesh_lights": cornell_mesh_lights,
+    "cornell_smooth": cornell_smooth,
     "klein": klein_scene,
     "cornell_klein": cornell_klein,
     "curves": cornell_curves,
