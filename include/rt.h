@@ -527,6 +527,13 @@ int rt_step_rays(int scene, int n, const double* rays, const double* T_in, const
  * the render).  A test probe of the device's log against the C library's. */
 int rt_curve_depth_probe(int ctx, int n, const double* cps, const double* eps8, int32_t* out_depth);
 
+/* The kernels' lean f64 helpers over an array (a test probe): out[i] = the helper `kind` of in[i].
+ * RT_F64_SQRT_MID / RT_F64_RCP_MID: sqrt(x) / 1.0 / x for every x, by the unscaled core sequence where x
+ * is finite, positive and in [2^-256, 2^256), else by the plain operation.  RT_F64_SQRT_CORE /
+ * RT_F64_RCP_CORE: the core sequence alone, which equals the IEEE result only inside that window. */
+enum { RT_F64_SQRT_MID = 0, RT_F64_RCP_MID = 1, RT_F64_SQRT_CORE = 2, RT_F64_RCP_CORE = 3 };
+int rt_f64_probe(int ctx, int kind, const double* in, int n, double* out);
+
 /* Statistics of the last render on this scene. */
 typedef struct rt_stats {
     uint64_t segments;    /* closest-hit queries issued by the integrator (ray segments) */

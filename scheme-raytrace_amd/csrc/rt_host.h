@@ -5,7 +5,7 @@
 //   rt_build.cpp     the host scene of a commit: flattening, BVH builds, records (build_scene; no HIP)
 //   rt_commit.cpp    its upload and the device-dependent sizing (commit_scene)
 //   rt_render.cpp    the render scheduler (render_impl; its arithmetic: rt_plan.h) and the render / resolve entry points
-//   rt_probe.cpp     the probe entry points (rt_hit_rays*, rt_light_probe, rt_step_rays, rt_curve_depth_probe)
+//   rt_probe.cpp     the probe entry points (rt_hit_rays*, rt_light_probe, rt_step_rays, rt_curve_depth_probe, rt_f64_probe)
 //   rt_gather.cpp    the frame-end gather (RCCL and in-process)
 //   rt_adaptive.cpp  adaptive sampling
 //   rt_features.cpp  first-hit feature buffers

@@ -39,6 +39,7 @@
 #include "rt_device.h"
 #include "rt_launch.h"
 #include "rt_boxray.h"
+#include "rt_f64.h"
 #include "rt_libm.h"
 #include "rt_wave.h"
 #include <cstdio>
@@ -84,7 +85,9 @@ __device__ __forceinline__ void philox10(uint32_t& c0, uint32_t& c1, uint32_t& c
     }
 }
 
-// (hi,lo) -> (2k+1)*2^-53 with k = (hi>>12)<<32 | lo; every step is exact.
+// (hi,lo) -> (2k+1)*2^-53 with k = (hi>>12)<<32 | lo; every step is exact.  The value u lies in
+// [2^-53, 1 - 2^-53], and so does 1 - u (exact: an odd multiple of 2^-53 again), far inside rt_f64.h's
+// window: sqrt_core(u) and sqrt_core(1 - u) need no guard.
 __device__ __forceinline__ double u32pair_unit(uint32_t hi, uint32_t lo) {
     const double k = (double)(hi >> 12) * 4294967296.0 + (double)lo;
     return (k * 2.0 + 1.0) * (1.0 / 9007199254740992.0);
@@ -164,8 +167,20 @@ __device__ __forceinline__ v3 operator-(v3 a, v3 b) { return mk(a.x - b.x, a.y -
 __device__ __forceinline__ v3 operator*(v3 a, v3 b) { return mk(a.x * b.x, a.y * b.y, a.z * b.z); }
 __device__ __forceinline__ v3 operator*(v3 a, double k) { return mk(a.x * k, a.y * k, a.z * k); }
 __device__ __forceinline__ double dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ double length(v3 a) { return sqrt(dot(a, a)); }
-__device__ __forceinline__ v3 unit(v3 a) { const double k = 1.0 / length(a); return a * k; }
+// sqrt and 1 / x by rt_f64.h's guarded cores: the same bits for every input.  unit: one guard serves both,
+// dot(a, a) in [2^-256, 2^256) puts the length in [2^-128, 2^128), inside the window again.
+// LEAN = false: the plain operations, which the curve code and the kernels of scenes with curves keep (the
+// guarded forms cost k_extend_curves time and the curve tails spilled registers: profiles/f64_lean/).
+template <bool LEAN = true>
+__device__ __forceinline__ double length(v3 a) { return LEAN ? sqrt_mid(dot(a, a)) : sqrt(dot(a, a)); }
+template <bool LEAN = true>
+__device__ __forceinline__ v3 unit(v3 a) {
+    const double aa = dot(a, a);
+    double k;
+    if (LEAN && __builtin_expect(f64_mid(aa), 1)) k = rcp_core(sqrt_core(aa));
+    else k = 1.0 / sqrt(aa);
+    return a * k;
+}
 #ifdef RT_F32_RECORDS
 __device__ __forceinline__ RayRec ray_rec(const v3 o, const v3 d) {
     return RayRec{(float)o.x, (float)o.y, (float)o.z, (float)d.x, (float)d.y, (float)d.z};
@@ -268,18 +283,21 @@ __global__ __launch_bounds__(256) void k_raygen(const DevScene sc, const RenderP
 constexpr double kInvPi = 1.0 / kPi;           // RN(1/pi): (/ x pi) = div_ia(x, kPi, kInvPi)
 // sphere test (geometry.scm:146-171); updates closest/best on a hit.
 // a = (dot d d), ia = 1/a (div_ia)
+template <bool LEAN = true>
 __device__ __forceinline__ void sphere_test(const v3 o, const v3 d, const double a, const double ia, const v3 c,
                                             const double rr, const int32_t id, double& closest, int32_t& best) {
     const v3 oc = o - c;
     const double b = dot(oc, d);
     const double cc = dot(oc, oc) - rr;
     const double disc = b * b - a * cc;
-    if (disc > 0.0) {
-        const double sq = sqrt(disc);
-        double t = div_ia(-b - sq, a, ia);
-        if (!(kTmin < t && t < closest)) t = div_ia(-b + sq, a, ia);
-        if (kTmin < t && t < closest) { closest = t; best = id; }
-    }
+    double sq;
+    // f64_mid(disc) implies disc > 0.0: the f64 compare is the other side's alone
+    if (LEAN && __builtin_expect(f64_mid(disc), 1)) sq = sqrt_core(disc);
+    else if (disc > 0.0) sq = sqrt(disc);
+    else return;
+    double t = div_ia(-b - sq, a, ia);
+    if (!(kTmin < t && t < closest)) t = div_ia(-b + sq, a, ia);
+    if (kTmin < t && t < closest) { closest = t; best = id; }
 }
 // center(time) of a moving sphere (geometry.scm:181-184): c0 + dc * frac, frac = (time - t0) / den.  How the
 // quotient is obtained (hoisted, DevScene::msph_shared, or LeafInfo's centre at time 0) is the caller's.
@@ -302,7 +320,7 @@ struct BezRay { double m[11]; };
 
 __device__ __forceinline__ void bez_ray(const v3 o, const v3 d, BezRay& R) {
     const double ox = -o.x, oy = -(-o.z), oz = -o.y;
-    const v3 rd = unit(d);
+    const v3 rd = unit<false>(d);
     const double lx = rd.x, ly = -rd.z, lz = rd.y;
     const double dd = sqrt(lx * lx + lz * lz);
     double r[9];
@@ -362,7 +380,7 @@ __device__ __forceinline__ v3 bez_tan(const Bez4& c, const bool one) {         /
     const v3 cb = ((c.p0 + c.p1 * -2.0) + c.p2) * 3.0;
     const v3 cc = (c.p1 - c.p0) * 3.0;
     const double k2 = one ? 3.0 : 0.0, k1 = one ? 2.0 : 0.0;
-    return unit((ca * k2 + cb * k1) + cc);
+    return unit<false>((ca * k2 + cb * k1) + cc);
 }
 __device__ __forceinline__ double dot2d(const v3 a, const v3 b) { return (a.x * b.x + a.y * b.y) + 0.0 * 0.0; }
 
@@ -1230,7 +1248,7 @@ __device__ __forceinline__ void bvh_closest_lane(const DevScene& sc, const v3 o,
                                                  const SphereRec* __restrict__ sph = nullptr,
                                                  const MSphereRec* __restrict__ msph = nullptr,
                                                  const int32_t* __restrict__ fid = nullptr) {
-    const double a = dot(d, d), ia = 1.0 / a;
+    const double a = dot(d, d), ia = WIDE ? 1.0 / a : rcp_mid(a);          // WIDE: scenes with curves
     constexpr bool SIGNED = sizeof(SE) == 2 && FROZEN;
     using BR = typename std::conditional<WIDE, BoxRayW, BoxRay>::type;
     BR br;
@@ -1249,26 +1267,26 @@ __device__ __forceinline__ void bvh_closest_lane(const DevScene& sc, const v3 o,
         if constexpr (DIRECT) {
             ++n_sph;
             const SphereRec S = fsph[k];
-            sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, k, closest, fbest);
+            sphere_test<!WIDE>(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, k, closest, fbest);
         } else {
             const BvhLeaf L = leaves[k];
             if (FROZEN) {
                 for (int s = L.sb; s < L.sb + L.sn; ++s) {
                     ++n_sph;
                     const SphereRec S = fsph[s];
-                    sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, s, closest, fbest);
+                    sphere_test<!WIDE>(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, s, closest, fbest);
                 }
             } else {
                 for (int s = L.sb; s < L.sb + L.sn; ++s) {
                     ++n_sph;
                     const SphereRec S = sph[s];
-                    sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, bs + s, closest, best);
+                    sphere_test<!WIDE>(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, bs + s, closest, best);
                 }
                 for (int s = L.mb; s < L.mb + L.mn; ++s) {
                     ++n_msph;
                     const MSphereRec S = msph[s];
                     const double frac = sc.msph_shared ? frac_shared : (time - S.t0) / S.den;
-                    sphere_test(o, d, a, ia, msphere_center(S, frac), S.rr, bm + s, closest, best);
+                    sphere_test<!WIDE>(o, d, a, ia, msphere_center(S, frac), S.rr, bm + s, closest, best);
                 }
             }
         }
@@ -1356,13 +1374,13 @@ __device__ __forceinline__ void bvh_closest_curves(const DevScene& sc, const v3 
                 const BvhLeaf L = sc.bleaf[~node];
                 for (int s = L.sb; s < L.sb + L.sn; ++s) {
                     const SphereRec S = sc.sph[s];
-                    sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, bs + s, closest, best);
+                    sphere_test<false>(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, bs + s, closest, best);
                 }
                 for (int s = L.mb; s < L.mb + L.mn; ++s) {
                     const MSphereRec S = sc.msph[s];
                     const double frac = (time - S.t0) / S.den;
                     const v3 cen = msphere_center(S, frac);
-                    sphere_test(o, d, a, ia, cen, S.rr, bm + s, closest, best);
+                    sphere_test<false>(o, d, a, ia, cen, S.rr, bm + s, closest, best);
                 }
                 pb = L.bb; pe = L.bb + L.bn;
                 ++n_leaf; n_cand += (uint32_t)L.bn;
@@ -1701,7 +1719,7 @@ __device__ __forceinline__ void bvh_closest_generic(const DevScene& sc, const v3
 
 // One non-BVH group of hit-obj-list (geometry.scm:33-50): its primitives in
 // list order against the shrinking closest.
-template <int F>
+template <int F, bool LEAN = (F & kFeatCurves) == 0>
 __device__ __forceinline__ void group_closest(const DevScene& sc, const Group& G, const v3 o0, const v3 d0,
                                               const double time, double& closest, int32_t& best, Rng* rng,
                                               bool* nan_t = nullptr) {
@@ -1716,7 +1734,7 @@ __device__ __forceinline__ void group_closest(const DevScene& sc, const Group& G
         for (int s = G.begin; s < G.end; ++s) {
             const SphereRec S = sc.sph[s];
             if constexpr (GEN) sphere_test_tie(sc, o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, base + s, closest, best);
-            else sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, base + s, closest, best);
+            else sphere_test<LEAN>(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, base + s, closest, best);
         }
     } else if (G.type == LEAF_MSPHERE) {               // geometry.scm:177-208
         const double a = dot(d, d), ia = 1.0 / a;
@@ -1730,7 +1748,7 @@ __device__ __forceinline__ void group_closest(const DevScene& sc, const Group& G
             }
             const v3 cen = msphere_center(S, frac);
             if constexpr (GEN) sphere_test_tie(sc, o, d, a, ia, cen, S.rr, base + s, closest, best);
-            else sphere_test(o, d, a, ia, cen, S.rr, base + s, closest, best);
+            else sphere_test<LEAN>(o, d, a, ia, cen, S.rr, base + s, closest, best);
         }
     } else if (G.type == LEAF_KLEIN) {                 // geometry.scm:645-673
         if (MED) {
@@ -1785,7 +1803,7 @@ __device__ __forceinline__ void group_closest(const DevScene& sc, const Group& G
 // grouped scan (their hit test draws random numbers; n_order is 0) — except media forests (kFeatGeneric |
 // kFeatExtra), whose list holds the media: each is tested at its position against the running closest and
 // draws from the path's stream there, as hit-obj-list does.
-template <int F>
+template <int F, bool LEAN = (F & kFeatCurves) == 0>
 __device__ __forceinline__ void list_closest(const DevScene& sc, const v3 o0, const v3 d0, const double time,
                                              double& closest, int32_t& best, Rng* rng = nullptr) {
     constexpr bool BEZ = (F & kFeatCurves) != 0;
@@ -1810,13 +1828,13 @@ __device__ __forceinline__ void list_closest(const DevScene& sc, const v3 o0, co
         if (type == LEAF_SPHERE) {
             const double a = dot(d, d), ia = 1.0 / a;
             const SphereRec S = sc.sph[s];
-            sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, id, closest, best);
+            sphere_test<LEAN>(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, id, closest, best);
         } else if (type == LEAF_MSPHERE) {
             const double a = dot(d, d), ia = 1.0 / a;
             const MSphereRec S = sc.msph[s];
             const double frac = (time - S.t0) / S.den;
             const v3 cen = msphere_center(S, frac);
-            sphere_test(o, d, a, ia, cen, S.rr, id, closest, best);
+            sphere_test<LEAN>(o, d, a, ia, cen, S.rr, id, closest, best);
         } else if (type == LEAF_KLEIN) {
             if (MED) {
                 double t;
@@ -1983,9 +2001,10 @@ __device__ __forceinline__ void put_sample(const RenderParams& rp, const uint32_
 __device__ __forceinline__ void write_sample(const RenderParams& rp, const PathRegs& p, const v3 L) {
     put_sample(rp, p.wid, p.T.x * L.x, p.T.y * L.y, p.T.z * L.z);
 }
+template <bool LEAN = true>
 __device__ __forceinline__ v3 sky_radiance(const DevScene& sc, const v3 d) {
     if (sc.sky != 0) return mk(0.0, 0.0, 0.0);            // black main.scm:97-98
-    const v3 ud = unit(d);                                 // sky-color main.scm:91-95
+    const v3 ud = unit<LEAN>(d);                           // sky-color main.scm:91-95
     const double s = 0.5 * (1.0 + ud.y);
     return mk(1.0, 1.0, 1.0) * (1.0 - s) + mk(0.5, 0.7, 1.0) * s;
 }
@@ -2090,7 +2109,7 @@ __global__ __launch_bounds__(256) void k_extend(const DevScene sc, const RenderP
             if (depth0) st.rng0[i] = g.ctr; else st.path[i].rng = g.ctr;
         }
         if (leaf < 0) {
-            const v3 L = sky_radiance(sc, d);
+            const v3 L = sky_radiance<(F & kFeatCurves) == 0>(sc, d);
             if (depth0) {                                // throughput 1: (* 1 x) = x
                 put_sample(rp, i, 1.0 * L.x, 1.0 * L.y, 1.0 * L.z);
             } else {
@@ -2275,7 +2294,7 @@ __global__ __launch_bounds__(256, kCurveWaves) void k_extend_curves(const DevSce
         ray_of(o, d, tm);
         closest = kTmax;
         best = -1;
-        for (int g = 0; g < gb; ++g) group_closest<0>(sc, sc.groups[g], o, d, tm, closest, best, nullptr);
+        for (int g = 0; g < gb; ++g) group_closest<0, false>(sc, sc.groups[g], o, d, tm, closest, best, nullptr);
         bcls = best >= 0 ? (int32_t)sc.leaf_cls[best] : -1;
         br = box_ray_w(o, d);
         tscale = fmax(1.0, 1.0 / sqrt(dot(d, d)));
@@ -2360,10 +2379,10 @@ __global__ __launch_bounds__(256, kCurveWaves) void k_extend_curves(const DevSce
                     load_path(st, h.slot, p, rp, h.leaf_dep >> kFuseLeafBits);
                     bool nan_t = false;
                     for (int g = gb + 1; g < sc.n_groups; ++g)
-                        group_closest<0>(sc, sc.groups[g], p.o, p.d, p.time, t, leaf, nullptr, &nan_t);
+                        group_closest<0, false>(sc, sc.groups[g], p.o, p.d, p.time, t, leaf, nullptr, &nan_t);
                     if (nan_t && sc.n_order > 0) list_closest<kFeatCurves>(sc, p.o, p.d, p.time, t, leaf);
                     v3 L;
-                    if (leaf < 0) L = sky_radiance(sc, p.d);
+                    if (leaf < 0) L = sky_radiance<false>(sc, p.d);
                     else go = fused_shade<FUSE == 2>(sc, rp, p, t, leaf, L);
                     if (go) {
                         store_path(st, h.slot, p);
@@ -2390,11 +2409,11 @@ __global__ __launch_bounds__(256, kCurveWaves) void k_extend_curves(const DevSce
                 ray_of(o, d, tm);
                 bool nan_t = false;
                 for (int g = gb + 1; g < sc.n_groups; ++g)
-                    group_closest<0>(sc, sc.groups[g], o, d, tm, closest, best, nullptr, &nan_t);
+                    group_closest<0, false>(sc, sc.groups[g], o, d, tm, closest, best, nullptr, &nan_t);
                 if (nan_t && sc.n_order > 0) list_closest<kFeatCurves>(sc, o, d, tm, closest, best);
                 if (gb + 1 < sc.n_groups && best >= 0) bcls = sc.leaf_cls[best];
                 if (best < 0) {
-                    const v3 L = sky_radiance(sc, d);
+                    const v3 L = sky_radiance<false>(sc, d);
                     if (depth0) {                            // throughput 1: (* 1 x) = x
                         put_sample(rp, i, 1.0 * L.x, 1.0 * L.y, 1.0 * L.z);
                     } else {
@@ -2535,13 +2554,13 @@ __global__ __launch_bounds__(256, kCurveWaves) void k_extend_curves(const DevSce
                     const double a = dot(d, d), ia = 1.0 / a;
                     for (int s = L.sb; s < L.sb + L.sn; ++s) {
                         const SphereRec S = sc.sph[s];
-                        sphere_test(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, bs + s, closest, best);
+                        sphere_test<false>(o, d, a, ia, mk(S.cx, S.cy, S.cz), S.rr, bs + s, closest, best);
                     }
                     for (int s = L.mb; s < L.mb + L.mn; ++s) {
                         const MSphereRec S = sc.msph[s];
                         const double frac = (tm - S.t0) / S.den;
                         const v3 cen = mk(S.c0x, S.c0y, S.c0z) + mk(S.dcx, S.dcy, S.dcz) * frac;
-                        sphere_test(o, d, a, ia, cen, S.rr, bm + s, closest, best);
+                        sphere_test<false>(o, d, a, ia, cen, S.rr, bm + s, closest, best);
                     }
                     bcls = best >= 0 ? (int32_t)sc.leaf_cls[best] : -1;
                 }
@@ -3282,7 +3301,8 @@ __device__ __forceinline__ void hit_record(const DevScene& sc, const LeafInfo& l
 // leaves: the leaf records (LDS in k_shade when the table is small, else HBM)
 // trig: rt_libm.h's sin / cos table for the lambertian bounce (an LDS copy in k_shade)
 // PT (lambertian only, a point-record queue): p.o is the hit point itself and p.d and t are not read
-template <int MATF, int TL = kTexPerlin, int LS = 1, bool EX = true, bool PT = false, bool TRI = !PT>
+// LEAN: rt_f64.h's forms (false: the kernels of scenes with curves)
+template <int MATF, int TL = kTexPerlin, int LS = 1, bool EX = true, bool PT = false, bool TRI = !PT, bool LEAN = true>
 __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P, const RenderParams& rp,
                                           PathRegs& p, const double t, const int32_t leaf, v3& L,
                                           const LeafInfo* __restrict__ leaves,
@@ -3311,9 +3331,9 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
     if (LS && mt == MAT_LAMBERTIAN && sc.light.type != LIGHT_OFF) {
         // pdf.scm mixture of (hitable-pdf light p) and (cosine-pdf normal)
         // (extension f2; oracle: rt_oracle.c light_pdf_value / light_random)
-        const v3 axis2 = unit(nrm);
+        const v3 axis2 = unit<LEAN>(nrm);
         const v3 a = (fabs(axis2.x) > 0.9) ? mk(0.0, 1.0, 0.0) : mk(1.0, 0.0, 0.0);
-        const v3 axis1 = unit(cross(axis2, a));
+        const v3 axis1 = unit<LEAN>(cross(axis2, a));
         const v3 axis0 = cross(axis2, axis1);
         const DevLight& Lt = sc.light;
         v3 dir;
@@ -3332,13 +3352,13 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
             const double z = sqrt(1.0 - r6);
             dir = (axis0 * x + axis1 * y) + axis2 * z;
         }
-        double cz = dot(unit(dir), axis2);
+        double cz = dot(unit<LEAN>(dir), axis2);
         const double cos_val = (cz > 0.0) ? div_ia(cz, kPi, kInvPi) : 0.0;
         double pdf_val;
         if constexpr (LS == 2) pdf_val = 0.5 * light_pdf_value(sc.lights, sc.n_lights, sc.lights_tri != 0, pt, dir) + 0.5 * cos_val;
         else pdf_val = 0.5 * light_pdf_value(Lt, pt, dir) + 0.5 * cos_val;
         if (!(pdf_val > 0.0)) return false;                 // no 0 * inf: the path ends (L = 0)
-        double cosine = dot(nrm, unit(dir));
+        double cosine = dot(nrm, unit<LEAN>(dir));
         if (cosine < 0.0) cosine = 0.0;
         const double spdf = div_ia(cosine, kPi, kInvPi);
         const double ipdf = 1.0 / pdf_val;
@@ -3348,9 +3368,9 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
         p.d = dir;
     } else if (mt == MAT_LAMBERTIAN) {                       // material.scm:24-39
         // onb.scm:8-16
-        const v3 axis2 = unit(nrm);
+        const v3 axis2 = unit<LEAN>(nrm);
         const v3 a = (fabs(axis2.x) > 0.9) ? mk(0.0, 1.0, 0.0) : mk(1.0, 0.0, 0.0);
-        const v3 axis1 = unit(cross(axis2, a));
+        const v3 axis1 = unit<LEAN>(cross(axis2, a));
         const v3 axis0 = cross(axis2, axis1);
         // (local uvw (random-cosine-direction)): `local` is a syntax-rules
         // macro (onb.scm:27-36), so random-cosine-direction (util.scm:37-44,
@@ -3362,23 +3382,24 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
         const double r6 = g.next();
         double c1, s3;
         bounce_cos_sin<EX>(2.0 * kPi * r1, 2.0 * kPi * r3, c1, s3, trig);
-        const double x = c1 * 2.0 * sqrt(r2);
-        const double y = s3 * 2.0 * sqrt(r4);
-        const double z = sqrt(1.0 - r6);
+        // the draws' square roots: u32pair_unit's range, no guard
+        const double x = c1 * 2.0 * (LEAN ? sqrt_core(r2) : sqrt(r2));
+        const double y = s3 * 2.0 * (LEAN ? sqrt_core(r4) : sqrt(r4));
+        const double z = LEAN ? sqrt_core(1.0 - r6) : sqrt(1.0 - r6);
         const v3 target = (axis0 * x + axis1 * y) + axis2 * z;   // onb `local`
-        const v3 sd = unit(target);
+        const v3 sd = unit<LEAN>(target);
         const double pdf = div_ia(dot(axis2, sd), kPi, kInvPi);
-        double cosine = dot(nrm, unit(sd));
+        double cosine = dot(nrm, unit<LEAN>(sd));
         if (cosine < 0.0) cosine = 0.0;
         const double spdf = div_ia(cosine, kPi, kInvPi);     // scattering-pdf
-        const double ipdf = 1.0 / pdf;
+        const double ipdf = LEAN ? rcp_mid(pdf) : 1.0 / pdf;
         const v3 att = leaf_tex<TL>(sc, P, li, pt, tu, tv);
         // forward form of  e + ((att*spdf) (*) L_next) * (1/pdf)  (main.scm:113-118)
         p.T = mk((p.T.x * (att.x * spdf)) * ipdf, (p.T.y * (att.y * spdf)) * ipdf,
                  (p.T.z * (att.z * spdf)) * ipdf);
         p.d = sd;
     } else if (mt == MAT_METAL) {                            // material.scm:45-57 (R2)
-        const v3 reflected = reflect(unit(rdir), nrm);
+        const v3 reflected = reflect(unit<LEAN>(rdir), nrm);
         v3 s;
         for (int it = 0;; ++it) {                            // util.scm:9-15
             const double a = g.next(), b = g.next(), c = g.next();
@@ -3397,15 +3418,15 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
         const double dd = dot(rdir, nrm);
         const v3 outward = (dd > 0.0) ? nrm * -1.0 : nrm;
         const double ni = (dd > 0.0) ? ref_idx : 1.0 / ref_idx;
-        const double cosine = (dd > 0.0) ? (dd * ref_idx) / length(rdir) : (-dd) / length(rdir);
+        const double cosine = (dd > 0.0) ? (dd * ref_idx) / length<LEAN>(rdir) : (-dd) / length<LEAN>(rdir);
         // refract :59-67 (raw v in the tangential term, Q5)
-        const v3 uv = unit(rdir);
+        const v3 uv = unit<LEAN>(rdir);
         const double dt = dot(uv, outward);
         const double disc = 1.0 - ni * ni * (1.0 - dt * dt);
         double prob = 1.0;
         v3 refracted = mk(0, 0, 0);
         if (disc > 0.0) {
-            refracted = (rdir - outward * dt) * ni - outward * sqrt(disc);
+            refracted = (rdir - outward * dt) * ni - outward * (LEAN ? sqrt_mid(disc) : sqrt(disc));
             const double r0a = (1.0 - ref_idx) / (1.0 + ref_idx);   // schlick :69-74
             const double r0 = r0a * r0a;
             prob = r0 + (1.0 - r0) * pow5(1.0 - cosine);
@@ -3424,7 +3445,7 @@ __device__ __forceinline__ bool shade_hit(const DevScene& sc, const PerlinLds& P
 template <bool EX>
 __device__ __forceinline__ bool fused_shade(const DevScene& sc, const RenderParams& rp, PathRegs& p, const double t,
                                             const int32_t leaf, v3& L) {
-    return shade_hit<-1, kTexPlain, 0, EX, false, false>(sc, *reinterpret_cast<const PerlinLds*>(sc.leaves), rp, p, t, leaf, L, sc.leaves);
+    return shade_hit<-1, kTexPlain, 0, EX, false, false, false>(sc, *reinterpret_cast<const PerlinLds*>(sc.leaves), rp, p, t, leaf, L, sc.leaves);
 }
 
 template <int TL = kTexPerlin>
@@ -3593,8 +3614,8 @@ __global__ __launch_bounds__(256, (finish_waves<F, TL, LSM>())) void k_finish(co
             if (MED) p.rng = g.ctr;
             v3 L;
             bool cont = false;
-            if (leaf < 0) L = sky_radiance(sc, p.d);
-            else cont = shade_hit<-1, TL, LSM, EX, false, (F & kFeatTri) != 0>(sc, P, rp, p, t, leaf, L, sc.leaves);
+            if (leaf < 0) L = sky_radiance<(F & kFeatCurves) == 0>(sc, p.d);
+            else cont = shade_hit<-1, TL, LSM, EX, false, (F & kFeatTri) != 0, (F & kFeatCurves) == 0>(sc, P, rp, p, t, leaf, L, sc.leaves);
             if (!cont) { write_sample(rp, p, L); active = false; }
         }
     }
@@ -4155,6 +4176,21 @@ __global__ __launch_bounds__(256) void k_curve_depth(const double* __restrict__ 
 hipError_t launch_curve_depth(const double* cps, const double* eps8, uint32_t n, int32_t* out, hipStream_t s) {
     if (n == 0u) return hipSuccess;
     hipLaunchKernelGGL(k_curve_depth, dim3((n + 255u) / 256u), dim3(256), 0, s, cps, eps8, n, out);
+    return hipGetLastError();
+}
+// rt_f64_probe: rt_f64.h's helpers over an array (kind: RT_F64_*; the core forms are the caller's to keep
+// inside the window)
+__global__ __launch_bounds__(256) void k_f64_probe(const int kind, const double* __restrict__ in, uint32_t n,
+                                                   double* __restrict__ out) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= n) return;
+    const double x = in[k];
+    out[k] = kind == RT_F64_SQRT_MID ? sqrt_mid(x) : kind == RT_F64_RCP_MID ? rcp_mid(x)
+           : kind == RT_F64_SQRT_CORE ? sqrt_core(x) : rcp_core(x);
+}
+hipError_t launch_f64_probe(int kind, const double* in, uint32_t n, double* out, hipStream_t s) {
+    if (n == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_f64_probe, dim3((n + 255u) / 256u), dim3(256), 0, s, kind, in, n, out);
     return hipGetLastError();
 }
 

@@ -67,6 +67,8 @@ bool point_hits_scene(const DevScene& sc);
 bool curve_persistent();                    // the host's check before a fused launch
 // rt_curve_depth_probe: bez_maxd on ray-space control points (12 doubles per curve) and 8 eps
 hipError_t launch_curve_depth(const double* cps, const double* eps8, uint32_t n, int32_t* out, hipStream_t s);
+// rt_f64_probe: rt_f64.h's helper `kind` (RT_F64_*) over n doubles
+hipError_t launch_f64_probe(int kind, const double* in, uint32_t n, double* out, hipStream_t s);
 // rt_hit_rays: n rays of 7 doubles (origin, direction, time); the closest hit's t and material
 hipError_t launch_hit_rays(const DevScene& sc, const double* rays, uint32_t n, double* out_t, int32_t* out_mat,
                            hipStream_t s);

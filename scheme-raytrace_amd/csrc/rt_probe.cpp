@@ -1,5 +1,6 @@
 // rt_probe.cpp — the C ABI's probe entry points: single kernels and single steps of a render on the
-// caller's arrays (closest-hit walks, the light sampler, one wavefront step or tail, the curve depth bound).
+// caller's arrays (closest-hit walks, the light sampler, one wavefront step or tail, the curve depth bound,
+// the lean f64 helpers).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -401,6 +402,22 @@ int rt_curve_depth_probe(int ctx, int n, const double* cps, const double* eps8, 
     TRY(p.in(eps8, n, &d_eps));
     TRY(p.out(out_depth, n, &d_out));
     HIPCHK(launch_curve_depth(d_cps, d_eps, (uint32_t)n, d_out, p.st));
+    return p.finish();
+}
+
+int rt_f64_probe(int ctx, int kind, const double* in, int n, double* out) {
+    LOCK_CTX(c, ctx);
+    if (kind < RT_F64_SQRT_MID || kind > RT_F64_RCP_CORE) return fail("rt_f64_probe: unknown kind " + std::to_string(kind));
+    if (n < 0) return fail("value count must be >= 0");
+    if (n == 0) return 0;
+    if (!in || !out) return fail("null pointer");
+    Probe p;
+    const double* d_in;
+    double* d_out;
+    TRY(p.begin(c, false));
+    TRY(p.in(in, (size_t)n, &d_in));
+    TRY(p.out(out, (size_t)n, &d_out));
+    HIPCHK(launch_f64_probe(kind, d_in, (uint32_t)n, d_out, p.st));
     return p.finish();
 }
 

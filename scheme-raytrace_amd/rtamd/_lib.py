@@ -177,6 +177,7 @@ _SIGNATURES = {
                      ctypes.c_int, _c_i32_p, _c_double_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_uint32),
                      _c_double_p, _c_i32_p, _c_i32_p, ctypes.POINTER(ctypes.c_uint32)],
     "rt_curve_depth_probe": [ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p, _c_i32_p],
+    "rt_f64_probe": [ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p],
     "rt_comm_unique_id": [ctypes.POINTER(ctypes.c_uint8)],
     "rt_comm_create": [ctypes.c_int, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int, ctypes.c_int, _c_int_p],
     "rt_comm_destroy": [ctypes.c_int],
@@ -220,7 +221,7 @@ EXPORTED = sorted(list(_SIGNATURES) + ["rt_last_error"])
 #: entry points a library built from an earlier commit may lack when RTAMD_LIB names one for an A/B measurement
 #: (tools/smooth_normals_report.py --parent): lib() loads such a library without them, and calling one raises
 #: RtError.  The in-tree build must export them all (EXPORTED; __graft_entry__.build() checks it).
-OPTIONAL = frozenset(["rt_add_mesh_normals"])
+OPTIONAL = frozenset(["rt_add_mesh_normals", "rt_f64_probe"])
 
 _lib = None
 

@@ -600,6 +600,19 @@ def curve_depth_probe(cps, eps8, ctx=None):
     return out
 
 
+F64_KINDS = {"sqrt_mid": 0, "rcp_mid": 1, "sqrt_core": 2, "rcp_core": 3}    # include/rt.h RT_F64_*
+
+
+def f64_probe(kind, values, ctx=None):
+    """rt_f64_probe: the kernels' sqrt / reciprocal helper `kind` (F64_KINDS) of every value; float64."""
+    ctx = ctx or default_context()
+    x = np.ascontiguousarray(values, dtype=np.float64).ravel()
+    out = np.zeros(x.size, dtype=np.float64)
+    dp = ctypes.POINTER(ctypes.c_double)
+    call("rt_f64_probe", ctx.handle, F64_KINDS[kind], x.ctypes.data_as(dp), x.size, out.ctypes.data_as(dp))
+    return out
+
+
 def comm_unique_id():
     """rt_comm_unique_id: a new communicator id (RT_COMM_ID_BYTES bytes), made by rank 0."""
     buf = (ctypes.c_uint8 * _lib.RT_COMM_ID_BYTES)()
